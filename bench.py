@@ -12,12 +12,17 @@ inside the timed region, as the north star asks.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N              # without RANK in the environment: re-executes itself under torch.distributed.run
-    python bench.py --extras              # + latency, PCIe, the other configs, ingest flood, fee grind, recovery, key-reuse sweep
+    python bench.py --full                # + the steady-state loop, the roofline loops, host-to-host, strong scaling, CPU baseline
+    python bench.py --extras              # --full + latency, PCIe, the other configs, ingest flood, fee grind, recovery, key-reuse sweep
+    python bench.py --dump-outputs DIR    # + the verdicts of the last timed step as DIR/<name>.npy (float32)
 
-stdout carries exactly ONE JSON line of at most LINE_LIMIT bytes (rank 0): the contract's keys,
-`roofline` (HIP-event timing of the dominant kernel), `cpu_baseline` (the CPU oracle on a bounded
-sample of the same rows, timed on this host's cores; its verdicts must equal the GPU's) and
-`parity`.  Everything else a run measures goes to `bench_details.json` (next to this file, and
+A plain run sets up, warms up, times --steps steps of the headline loop and prints the line: the
+contract's keys, `config` and `parity` (the last timed step's verdicts against the ones known by
+construction).  Everything else is measured under --full (--extras, --roofline-only and --ab imply it).
+stdout carries exactly ONE JSON line of at most LINE_LIMIT bytes (rank 0).  Under --full it also
+holds `roofline` (HIP-event timing of the dominant kernel) and `cpu_baseline` (the CPU oracle on a
+bounded sample of the same rows, timed on this host's cores; its verdicts must equal the GPU's,
+counted in `parity`).  Everything else a --full run measures goes to `bench_details.json` (next to this file, and
 under gpurun_out/ when that directory exists) and, as one line, to stderr.  One number per run,
 as the reference's own micro-benchmark prints it (onchaind/test/run-grind_feerate.c:146-154).
 """
@@ -110,31 +115,36 @@ REQUIRED = {"": LINE_KEYS + ("config", "roofline", "cpu_baseline", "parity"),
             "config": ("workload", "rows_per_gpu_per_step", "parallelism"),
             "roofline": ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "rows_in_launch"),
             "parity": ("rows_checked", "mismatches")}
+# the line of a plain run (no --full): the headline loop is all it measures
+REQUIRED_PLAIN = {"": LINE_KEYS + ("config", "parity"), "config": REQUIRED["config"], "parity": REQUIRED["parity"]}
 
 
-def compact_line(d):
+def compact_line(d, plain=False):
     """the details dict of a run -> the dict printed as the ONE stdout line: the bench contract's keys, `config`, `roofline`, `cpu_baseline`
     and `parity` cut to the keys above; notes and sub-reports stay in bench_details.json.  Raises when a required key is missing or the
-    line would not fit LINE_LIMIT (tests/test_bench_line.py runs this on canned numbers)."""
+    line would not fit LINE_LIMIT (tests/test_bench_line.py runs this on canned numbers).  plain: the line of a run without --full --
+    the contract's keys, `config` and `parity`, no side file."""
     line = {k: d[k] for k in LINE_KEYS}
     line["config"] = {k: d["config"][k] for k in CONFIG_KEYS if d["config"].get(k) is not None}
-    line["roofline"] = {k: d["roofline"].get(k) for k in ROOFLINE_KEYS if k in d["roofline"]}
-    cb = d.get("cpu_baseline")
-    if cb is not None:
-        cb = {k: cb[k] for k in CPU_KEYS if cb.get(k) is not None}
-        for k in ("note", "sample"):
-            if len(str(cb.get(k, ""))) > 160:
-                cb[k] = str(cb[k])[:157] + "..."
-    line["cpu_baseline"] = cb
+    if not plain:
+        line["roofline"] = {k: d["roofline"].get(k) for k in ROOFLINE_KEYS if k in d["roofline"]}
+        cb = d.get("cpu_baseline")
+        if cb is not None:
+            cb = {k: cb[k] for k in CPU_KEYS if cb.get(k) is not None}
+            for k in ("note", "sample"):
+                if len(str(cb.get(k, ""))) > 160:
+                    cb[k] = str(cb[k])[:157] + "..."
+        line["cpu_baseline"] = cb
     line["parity"] = {k: d["parity"][k] for k in PARITY_KEYS if k in d["parity"]}
     if d.get("steady_state"):
         line["steady_state"] = {k: d["steady_state"][k] for k in ("value", "steps", "ms_per_step")}
     if d.get("sharded_configs"):
         line["sharded_configs"] = {name: {k: v[k] for k in ("verifies_per_s", "ms", "ranks", "mismatches", "scaling") if k in v}
                                    for name, v in d["sharded_configs"].items()}
-    line["details"] = d.get("details_file", "bench_details.json")
+    if not plain:
+        line["details"] = d.get("details_file", "bench_details.json")
     line = _r(line)
-    for sect, keys in REQUIRED.items():
+    for sect, keys in (REQUIRED_PLAIN if plain else REQUIRED).items():
         have = line if sect == "" else line[sect]
         missing = [k for k in keys if k not in have]
         if missing:
@@ -163,6 +173,37 @@ def write_outputs(details, json_fd, details_path=None):
     sys.stderr.flush()
     os.write(json_fd, (text + "\n").encode())
     return line
+
+
+DUMP_LIMIT = 60_000_000     # bytes of all --dump-outputs files together (64 MB at most, .npy headers included)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of {name: 1-D array} as <dirname>/<name>.npy in float32.  An array too large for its share of DUMP_LIMIT
+    is cut to a fixed, seeded sample of its rows (the same rows in every run of the same size), their indices beside it as <name>_rows.npy"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT // (12 * len(arrays))        # a sampled row costs 4 bytes of value + 8 of index
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        if a.size > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
+
+
+def headline(world, n, steps, warmup, dt, roofline_only=False):
+    """the bench contract's keys and `config`: the same in a plain run and under --full"""
+    return {
+        "metric": "signature verifies/sec (ECDSA+Schnorr mix)", "value": world * 2 * n * steps / dt, "unit": "verifies/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 (256-bit modular integer)",
+        "data": "synthetic",
+        "config": {"workload": "configs[1]+configs[2]: %d ECDSA (65-byte keys, 65536 distinct) + %d BIP-340 Schnorr per GPU per step, "
+                               "90%% valid / 10%% invalid, inputs resident in HBM%s" % (n, n, "; --roofline-only: the chained loop" if roofline_only else ""),
+                   "rows_per_gpu_per_step": 2 * n, "parallelism": "shard-by-row x%d, RCCL all-gather of verdicts" % world,
+                   "key_table_cache": "off (tables rebuilt every call)"}}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -782,9 +823,14 @@ def main():
                          "--kernel-trace --stats` over this command is directly comparable with roofline.avg_launch_ms")
     ap.add_argument("--ab", action="store_true", help="A/B runs: the cold loop, the chained loop and the isolated calls only")
     ap.add_argument("--steady-steps", type=int, default=250,
-                    help="when --steps gives a timed region under ~1 s: steps of an extra, longer cold loop reported as `steady_state` (0 = skip)")
+                    help="--full, when --steps gives a timed region under ~1 s: steps of an extra, longer cold loop reported as `steady_state` (0 = skip)")
     ap.add_argument("--h2h-steps", type=int, default=60, help="steps of each host-to-host leg")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline loop: the steady-state loop, the chained and isolated roofline loops, the "
+                                                        "multiply-add peak, host-to-host, strong scaling / sharded configs, the CPU baseline, bench_details.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the headline loop's last timed step as DIR/<name>.npy (float32; the same inputs in every run)")
     args = ap.parse_args()
+    args.full = args.full or args.extras or args.roofline_only or args.ab
     if args.gpus > 1 and "RANK" not in os.environ:
         # a plain `python bench.py --gpus N`: become the launcher -- one process per GPU over RCCL, rendezvous on 127.0.0.1
         import socket
@@ -943,13 +989,39 @@ def main():
                 r[int(inf["last_mode"])] = int(inf["last_hot_rows"])
         return r
 
+    def last_outputs():
+        # what a caller of the timed path holds after its last step: the verdict vectors (with several ranks the all-gathered ones)
+        if multi:
+            return {"ecdsa_ok": ok_all_e.cpu().numpy(), "schnorr_ok": ok_all_s.cpu().numpy()}
+        return {"ecdsa_ok": ok_e[(stepno[0] - 1) % len(ok_e)].cpu().numpy(), "schnorr_ok": ok_s[(stepno[0] - 1) % len(ok_s)].cpu().numpy()}
+
     # the headline first: cold, every table rebuilt in every call
     full = not args.roofline_only
     default_legs = full and not args.ab
-    dt, mism_cold, steady = float("nan"), 0, None
+    dt, mism_cold, steady, outputs = float("nan"), 0, None, None
     if full:
         with clock("headline_loop"):
             dt, mism_cold = timed(eng_cold)
+        if args.dump_outputs:
+            outputs = last_outputs()
+        if not args.full:
+            # a plain run: the headline loop is all its line needs
+            if multi:
+                m = torch.tensor([mism_cold], dtype=torch.int64, device=device)
+                dist.all_reduce(m)
+                mism_cold = int(m.item())
+            if rank == 0:
+                if outputs is not None:
+                    dump_outputs(args.dump_outputs, outputs)
+                out = dict(headline(world, n, args.steps, args.warmup, dt), parity={"rows_checked": world * 2 * n, "mismatches": mism_cold})
+                os.write(json_fd, (compact_line(out, plain=True)[1] + "\n").encode())
+            eng_cold.close()
+            if multi:
+                dist.barrier()
+                dist.destroy_process_group()
+            if not args.no_parity and rank == 0 and mism_cold:
+                raise SystemExit("PARITY FAILURE: %d mismatching verdicts" % mism_cold)
+            return
         record_kernel_times(eng_cold)
         if args.steady_steps > 0 and dt < 1.0 and not multi:
             # the driver's --steps 20 is a 0.17 s region: the same loop once more over a region of seconds, reported beside `value`
@@ -975,6 +1047,8 @@ def main():
             if not full:
                 record_kernel_times(eng_cold)
                 dt = dt_ch
+                if args.dump_outputs:
+                    outputs = last_outputs()
             eng_cold.set_ecmult_chain(False)
             if lm_cold is not None:
                 launch_ms[id(eng_cold)] = lm_cold
@@ -1040,8 +1114,7 @@ def main():
 
     out = None
     if rank == 0:
-        total = world * 2 * n * args.steps
-        value = total / dt
+        value = world * 2 * n * args.steps / dt
         # ---- roofline of the dominant kernel, k_ecmult_keyed<false, 3>.  Numerator: the 32x32->64 multiply-adds the kernel's
         # algorithm EXECUTES per row (W_EXEC) x the rows its launches carried.  Denominator: the average duration of those launches, HIP events
         # on the launching lane's stream right around every one of them, in the CHAINED loop (one such launch in flight at a time: the brackets do
@@ -1148,15 +1221,7 @@ def main():
         algo_bytes = BYTES_ECDSA65 * n
         ke = np.mean(np.array(kernel_ms["ecdsa"]), axis=0)      # prep, keys, ecmult [ms]
         ks = np.mean(np.array(kernel_ms["schnorr"]), axis=0)
-        out = {
-            "metric": "signature verifies/sec (ECDSA+Schnorr mix)", "value": value, "unit": "verifies/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32 (256-bit modular integer)",
-            "data": "synthetic",
-            "config": {"workload": "configs[1]+configs[2]: %d ECDSA (65-byte keys, 65536 distinct) + %d BIP-340 Schnorr per GPU per step, "
-                                   "90%% valid / 10%% invalid, inputs resident in HBM%s" % (n, n, "" if full else "; --roofline-only: the chained loop"),
-                       "rows_per_gpu_per_step": 2 * n, "parallelism": "shard-by-row x%d, RCCL all-gather of verdicts" % world,
-                       "key_table_cache": "off (tables rebuilt every call)"},
+        out = dict(headline(world, n, args.steps, args.warmup, dt, not full), **{
             "steady_state": steady,
             "rates": {"ecdsa65_verifies_per_s_1gpu": n / (ke.sum() * 1e-3), "schnorr_verifies_per_s_1gpu": n / (ks.sum() * 1e-3),
                       "kernel_ms_ecdsa": {"prep": ke[0], "keys_and_tables": ke[1], "ecmult": ke[2], "parity_stage": ke[3]},
@@ -1217,7 +1282,7 @@ def main():
                         "peak_GBs": HBM_PEAK_GBS, "frac": algo_bytes / t_ecmult / 1e9 / HBM_PEAK_GBS}}),
             "parity": {"rows_checked": world * 2 * n, "mismatches": mism, "mismatches_by_leg": {"cold_loops": mism_cold, "isolated_calls": mism_iso},
                        "against": "verdicts known by construction (all rows; the last timed step of every loop writes into poisoned verdict buffers)"},
-        }
+        })
         if sharded is not None:
             out["sharded_configs"] = {k: v for k, v in sharded.items() if isinstance(v, dict)}
         # ---- the metric as SURVEY 8(d) words it: host buffers in -> verdicts in host memory out (never `value`; config.value_host_to_host)
@@ -1269,6 +1334,8 @@ def main():
             out["cpu_baseline"] = None
         out["phase_seconds"] = dict(clock.t, total=time.perf_counter() - t_start)
         out["host_numa"] = getattr(plat, "numa", None)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         write_outputs(out, json_fd, args.details)
         if eng_warm is not None:
             eng_warm.close()

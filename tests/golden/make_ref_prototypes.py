@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Harvests the prototypes of the reference's signature-check boundary from the Core Lightning tree and writes
 them, whitespace-normalised, to tests/golden/ref_prototypes.json.  tests/test_abi.py requires include/cln_shim.h to hold each of
-them token for token; when /root/reference is present the test also re-runs this harvest and requires the fixture to be current.
+them token for token; when LAMD_REFERENCE_TREE names a Core Lightning tree the test also re-runs this harvest and requires the fixture
+to be current.
 
-    python tests/golden/make_ref_prototypes.py [/root/reference]
+    python tests/golden/make_ref_prototypes.py <Core Lightning tree>
 """
 import json
 import os

@@ -3,8 +3,10 @@
 * the line is built from a details dict by `bench.compact_line`: canned numbers in, at most LINE_LIMIT bytes out, every key the bench contract
   names present, a dict that would not fit refused;
 * bench.py itself, launched exactly as the driver launches it (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
-  --steps K --warmup W`), at world 1, 2 and 8 over gloo with tests/bench_stub.py in the engine's place: ONE line on stdout, n_gpus = world,
-  the sharded configs present with the whole verdict vector on every rank, no mismatches.
+  --steps K --warmup W --full`), at world 1, 2 and 8 over gloo with tests/bench_stub.py in the engine's place: ONE line on stdout, n_gpus = world,
+  the sharded configs present with the whole verdict vector on every rank, no mismatches;
+* a plain run (no --full) at world 1 and 2: the headline loop only, the contract's keys on the line, and --dump-outputs writing the
+  last step's verdicts, the same in two runs.
 No GPU, no oracle: what is tested is the bench's own plumbing."""
 import copy
 import json
@@ -98,7 +100,7 @@ def test_floats_are_rounded_and_non_finite_ones_become_null():
     assert bench._r({"a": [1.23456789012, float("nan")], "b": True, "c": 7, "d": float("inf")}) == {"a": [1.23457, None], "b": True, "c": 7, "d": None}
 
 
-def _run_bench(world, tmp_path, extra=()):
+def _run_bench(world, tmp_path, extra=("--full",)):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
@@ -118,7 +120,7 @@ def _run_bench(world, tmp_path, extra=()):
     lines = [l for l in p.stdout.split("\n") if l.strip()]
     assert len(lines) == 1, "stdout must carry exactly one line: %r" % p.stdout[:2000]
     assert len(lines[0]) < bench.LINE_LIMIT
-    return json.loads(lines[0]), json.load(open(details)), p.stderr
+    return json.loads(lines[0]), (json.load(open(details)) if "--full" in extra else None), p.stderr
 
 
 def test_bench_with_one_rank_over_the_stub(tmp_path):
@@ -155,3 +157,46 @@ def test_bench_multi_rank_path_under_gloo(world, tmp_path):
     assert len(d4["shard_messages"]) == 2 and all(len(k) == world for k in d4["shard_messages"]) and d4["one_cut_ms"] > 0
     assert d5["verdicts_on_every_rank"] == d5["verifies"] == sum(d5["shard_rows"]["ecdsa"]) + sum(d5["shard_rows"]["schnorr"])
     assert all(r % 484 == 0 for rows in d5["shard_rows"].values() for r in rows)          # a commitment's 484 signatures stay on one rank
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(world, tmp_path):
+    """no --full: the line holds the contract's keys, `config` and `parity` and nothing the other legs measure, no side file is written, and
+    --dump-outputs leaves the last timed step's verdicts (the all-gathered ones with two ranks) as float32, identical in a second run"""
+    dumps = [tmp_path / "out_a", tmp_path / "out_b"]
+    for d in dumps:
+        line, det, err = _run_bench(world, tmp_path, ["--dump-outputs", str(d)])
+        assert det is None and not (tmp_path / ("details_%d.json" % world)).exists() and "BENCH_DETAILS" not in err
+        for k in bench.LINE_KEYS + ("config", "parity"):
+            assert k in line, k
+        for k in ("roofline", "cpu_baseline", "steady_state", "sharded_configs", "details"):
+            assert k not in line, k
+        assert line["n_gpus"] == world and line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "verifies/s" and line["higher_is_better"] is True
+        assert line["parity"] == {"rows_checked": world * 4000, "mismatches": 0}
+        assert abs(line["value"] - world * 4000 * 3 / (line["ms_per_step"] * 3e-3)) / line["value"] < 1e-3
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bench_stub
+    import numpy as np
+    import torch
+    for name, make in (("ecdsa_ok", bench_stub.make_ecdsa), ("schnorr_ok", bench_stub.make_schnorr)):
+        a, b = (np.load(str(d / (name + ".npy"))) for d in dumps)
+        assert a.dtype == np.float32 and a.shape == (world * 2000,) and np.array_equal(a, b)
+        seed = bench_stub.SEED_CFG2 if name == "ecdsa_ok" else bench_stub.SEED_CFG3
+        want = np.concatenate([make(None, 2000, seed=seed + r).expect for r in range(world)])
+        assert np.array_equal(a, want.astype(np.float32))
+    assert sorted(os.listdir(str(dumps[0]))) == ["ecdsa_ok.npy", "schnorr_ok.npy"]
+
+
+def test_dump_of_a_large_output_is_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 12 * 2 * 1000)
+    big = {"a": np.arange(5000) % 2, "b": np.ones(700, np.uint8)}
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(str(tmp_path / "x" / f)) for f in os.listdir(str(tmp_path / "x")))
+    assert total <= 12 * 2 * 1000 + 4 * 128
+    rows = np.load(str(tmp_path / "x" / "a_rows.npy"))
+    a = np.load(str(tmp_path / "x" / "a.npy"))
+    assert rows.dtype == np.float64 and a.dtype == np.float32 and len(rows) == len(a) == 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a, (rows % 2).astype(np.float32)) and np.array_equal(rows, np.load(str(tmp_path / "y" / "a_rows.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "x" / "b.npy")), np.ones(700, np.float32)) and not (tmp_path / "x" / "b_rows.npy").exists()

@@ -6,8 +6,11 @@ GPU part (-m gpu): the real engine behind the server, 8 client processes issuing
 engine's and the oracle's."""
 import ctypes
 import os
+import pathlib
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -82,12 +85,30 @@ def _stop(p):
     return out
 
 
+def _short_dir():
+    """a fresh private directory for unix sockets: a socket path must fit sun_path (108 bytes), and pytest's own temporary directories can lie
+    deeper than that"""
+    for base in (tempfile.gettempdir(), "/tmp"):
+        if len(base) <= 48 and os.access(base, os.W_OK | os.X_OK):
+            return tempfile.mkdtemp(prefix="lamd-", dir=base)
+    raise RuntimeError("no temporary directory with a path short enough for a unix socket")
+
+
+@pytest.fixture
+def sockdir():
+    d = _short_dir()
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    d = tmp_path_factory.mktemp("served")
-    so = str(d / "libstub_engine.so")
+    """(the stub engine library, a short directory for the sockets of the stub-backed tests)"""
+    so = str(tmp_path_factory.mktemp("served") / "libstub_engine.so")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-shared", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-o", so, os.path.join(ROOT, "tests", "c", "stub_engine.c")])
-    return so, str(d)
+    d = _short_dir()
+    yield so, d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 def _connect(L, sock):
@@ -469,9 +490,9 @@ def test_streams_of_eight_client_processes_share_the_engine_flushes(stub, mode, 
         _stop(p)
 
 
-def test_without_a_server_everything_fails_closed(stub, tmp_path):
+def test_without_a_server_everything_fails_closed(stub, sockdir):
     L = _client()
-    rc, ctx = _connect(L, str(tmp_path / "nobody.sock"))
+    rc, ctx = _connect(L, os.path.join(sockdir, "nobody.sock"))
     assert rc == -1 and b"no lamd_served" in L.lamd_last_error(ctx)
     L.lamd_shutdown(ctx)
     # ... and so does the mirror built on the client library: check_signed_hash() is false, sigcheck_* returns an "engine error" string
@@ -490,7 +511,7 @@ def test_without_a_server_everything_fails_closed(stub, tmp_path):
     assert r.returncode == 1 and "lamd_init" in r.stderr
 
 
-def test_the_client_trusts_only_a_server_of_its_own_user_and_there_is_no_default_under_tmp(stub, tmp_path):
+def test_the_client_trusts_only_a_server_of_its_own_user_and_there_is_no_default_under_tmp(stub, sockdir):
     """whoever binds a world-writable path first would answer every check with "good".  No default path outside LAMD_SERVED_SOCKET /
     XDG_RUNTIME_DIR; the client checks SO_PEERCRED and the socket file's owner; the server binds 0600 from the start, does not replace a path it does
     not own, and a raw PUBKEY_PARSE with a bad key length fails instead of answering rc 0 with stale bytes."""
@@ -507,8 +528,8 @@ def test_the_client_trusts_only_a_server_of_its_own_user_and_there_is_no_default
     r = subprocess.run([sys.executable, "-c", code, _build.build_served()[1]], capture_output=True, text=True, timeout=30, env=env)
     assert r.stdout.startswith("-1 ") and "LAMD_SERVED_SOCKET" in r.stdout
     # XDG_RUNTIME_DIR is the default's home
-    sock = str(tmp_path / "lamd_served.sock")
-    env2 = dict(env, XDG_RUNTIME_DIR=str(tmp_path))
+    sock = os.path.join(sockdir, "lamd_served.sock")
+    env2 = dict(env, XDG_RUNTIME_DIR=sockdir)
     p = subprocess.Popen([served, "--engine", so], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env2)
     try:
         assert "ready on " + sock in p.stdout.readline()
@@ -544,7 +565,7 @@ def test_the_client_trusts_only_a_server_of_its_own_user_and_there_is_no_default
     finally:
         _stop(p)
     # a path that exists and is not a socket of this user is not replaced
-    victim = tmp_path / "notasocket"
+    victim = pathlib.Path(sockdir) / "notasocket"
     victim.write_text("x")
     r = subprocess.run([served, "--engine", so, "--socket", str(victim)], capture_output=True, text=True, timeout=30, env=env)
     assert r.returncode == 1 and "not replacing" in r.stderr and victim.read_text() == "x"
@@ -582,11 +603,11 @@ print("bad", bad)
 
 
 @pytest.mark.gpu
-def test_eight_client_processes_share_one_engine(orc, kat, tmp_path):
+def test_eight_client_processes_share_one_engine(orc, kat, tmp_path, sockdir):
     """the real engine behind lamd_served: 8 client processes, each validating its own channels' commitments (1 + 483 signatures per request, the htlc key
     recurring) -- every verdict equals the oracle's, the server merged concurrent requests into shared launches, and the mirror over the client
     library (liblightning_amd_cln_client.so) gives the reference's answers"""
-    sock = str(tmp_path / "gpu.sock")
+    sock = os.path.join(sockdir, "gpu.sock")
     p = _start(sock)
     try:
         files = []
@@ -688,7 +709,7 @@ print("bad %d rows %d t0 %.6f t1 %.6f" % (bad0 + bad, rows, t0, t1))
 
 
 @pytest.mark.gpu
-def test_eight_client_processes_stream_their_commitments_through_the_service(tmp_path):
+def test_eight_client_processes_stream_their_commitments_through_the_service(tmp_path, sockdir):
     """VERDICT r05 "next" 8: BASELINE configs[4] as channelds see it -- 8 client processes, each STREAMING its channels' commitments (flushes kept in
     flight: lamd_queue_*_batch / lamd_flush / lamd_wait of the client library) through ONE lamd_served.  Every verdict equals construction (= the
     in-process engine's, checked on the same rows), and the rate of the whole job is compared with the same job streamed by one in-process
@@ -741,7 +762,7 @@ def test_eight_client_processes_stream_their_commitments_through_the_service(tmp
     finally:
         eng.close()
     torch.cuda.synchronize()
-    sock = str(tmp_path / "stream.sock")
+    sock = os.path.join(sockdir, "stream.sock")
     p = _start(sock)
     try:
         files, go = [], str(tmp_path / "go")

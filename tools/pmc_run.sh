@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/pmc_${1:-r02}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # the roofline loop only (cold engine, chained ecmult launches): every k_ecmult_keyed<false, 3> launch of the process is one of that loop's
-CMD="python $R/bench.py --roofline-only --steps ${PMC_STEPS:-6} --warmup 2"
+CMD="python $R/bench.py --full --roofline-only --steps ${PMC_STEPS:-6} --warmup 2"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.json 2> $OUT/trace.err
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > $OUT/fetch.json 2> $OUT/fetch.err
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > $OUT/write.json 2> $OUT/write.err
