@@ -283,9 +283,10 @@ int lamd_queue_reserve(lamd_ctx *ctx, size_t n, size_t keylen, uint8_t **hash32,
 /* In-place form for a host that ALREADY holds the rows in pinned memory (lamd_served: its clients' shared blocks): the n triples (keys packed, publen
  * / 32 bytes each) get tickets like the batch forms, but their bytes are not copied -- they cross the bus from the caller's buffers when the set is
  * flushed.  The buffers must stay unchanged until the flush that carries the rows has been collected (lamd_poll / lamd_wait).  Batches of <= 4 096
- * rows (the latency kernel reads the staging rows themselves) and rows in memory that is NOT pinned end to end are copied as by lamd_queue_*_batch.
- * lamd_host_register() pins a range for every device (hipHostRegister, portable): register whole, page-aligned blocks, once, and keep them
- * registered while rows of theirs are queued.
+ * rows (the latency kernel reads the staging rows themselves) are copied as by lamd_queue_*_batch, and so is every column that does not lie inside
+ * ONE range registered with lamd_host_register(): a column spanning two registrations, one with a pageable hole, and memory pinned by other means
+ * (hipHostMalloc, another library's registration) are copied.  lamd_host_register() pins a range for every device (hipHostRegister, portable):
+ * register whole, page-aligned blocks, once, and keep them registered while rows of theirs are queued.
  * Both may be called from any thread while another drives the context.  (Replaces nothing in the reference: the producer side of SURVEY.md 8(f)'s
  * sidecar, channeld/channeld.c:7063-7121 being one process per channel.) */
 int lamd_queue_ecdsa_batch_inplace(lamd_ctx *ctx, size_t n, const uint8_t *hash32, const uint8_t *sig64, const uint8_t *pubkey, size_t publen);
@@ -294,6 +295,8 @@ int lamd_host_register(lamd_ctx *ctx, void *p, size_t bytes);
 int lamd_host_unregister(lamd_ctx *ctx, void *p);
 /* The NUMA node device `device` hangs on (sysfs), -1 when unknown: run the producer threads and allocate the buffers that feed a device there. */
 int lamd_device_numa_node(int device);
+/* A failed flush (< 0) drops the rows queued since the previous flush: their tickets are void and no verdicts are reported for them; the
+ * engine has stopped reading their buffers (in-place rows included) when it returns, and the next flush carries only rows queued after it. */
 int lamd_flush(lamd_ctx *ctx);
 /* 1 = finished (ok[0..*n) filled, tickets in submission order), 0 = still running, < 0 error */
 int lamd_poll(lamd_ctx *ctx, uint8_t *ok, size_t cap, size_t *n);
@@ -359,6 +362,7 @@ typedef struct {
 	size_t keyed_ecmult_launches[2];
 	int hw_queues_env;        /* GPU_MAX_HW_QUEUES as lamd_init() found it (0 = unset: the runtime's default of 4; < 16 costs overlap between the lanes) */
 	int queue_sets;           /* staging sets of the streaming queue = the most flushes that may be outstanding */
+	size_t last_flush_inplace_rows; /* rows the last lamd_flush() sent to the device straight from the callers' registered memory (queued in place, not copied) */
 } lamd_info;
 int lamd_get_info(lamd_ctx *ctx, lamd_info *info);
 int lamd_get_lane_info(lamd_ctx *ctx, int lane, lamd_info *info); /* the last call that ran on lane 0 .. lanes-1 */

@@ -277,6 +277,11 @@ static int collect(lamd_ctx *c, uint8_t *ok, size_t cap, size_t *n, bool block) 
     if (s.busy && s.seq == c->oldest_seq) f = &s;
   if (!f) { c->err = "no flush outstanding"; return LAMD_ERR_STATE; }
   if (cap < f->n) { c->err = "verdict buffer smaller than the flush"; return LAMD_ERR_ARG; }
+  // every error from here on leaves the caller's verdicts zero: a caller that ignores the return code still reads "not verified"
+  auto refuse = [&](int rc) {
+    memset(ok, 0, f->n);
+    return rc;
+  };
   while (!c->arrived.count(f->seq)) {
     lamd_srv_rep rep;
     if (!block) {
@@ -284,21 +289,21 @@ static int collect(lamd_ctx *c, uint8_t *ok, size_t cap, size_t *n, bool block) 
       if (k < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) return 0;
       if (k >= 0 && (size_t)k < sizeof rep && k != 0) return 0;  // a reply is on its way
     }
-    if (!recv_all(c->fd, &rep, sizeof rep) || rep.magic != LAMD_SRV_MAGIC || rep.seq == 0) { c->err = "connection to lamd_served lost"; return LAMD_ERR_STATE; }
+    if (!recv_all(c->fd, &rep, sizeof rep) || rep.magic != LAMD_SRV_MAGIC || rep.seq == 0) { c->err = "connection to lamd_served lost"; return refuse(LAMD_ERR_STATE); }
     c->arrived[rep.seq] = rep;
   }
   const lamd_srv_rep rep = c->arrived[f->seq];
   c->arrived.erase(f->seq);
   f->busy = false;
   c->oldest_seq++;
-  if (rep.rc < 0) {
+  if (rep.rc != LAMD_OK) {
     char e[sizeof rep.err];
     memcpy(e, rep.err, sizeof e);
     e[sizeof e - 1] = 0;
     c->err = e;
-    return rep.rc;
+    return refuse(rep.rc < 0 ? rep.rc : LAMD_ERR_STATE);
   }
-  if (rep.out_offset + f->n > f->size) { c->err = "reply outside the flush block"; return LAMD_ERR_STATE; }
+  if (rep.out_offset > f->size || f->n > f->size - rep.out_offset) { c->err = "reply outside the flush block"; return refuse(LAMD_ERR_STATE); }
   memcpy(ok, f->p + rep.out_offset, f->n);
   *n = f->n;
   return 1;

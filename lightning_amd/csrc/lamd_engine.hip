@@ -19,6 +19,7 @@
 #include "../../include/lightning_amd_debug.h"
 #include "verify_core.h"
 #include "fuzz.h"
+#include "host_ranges.h"
 
 using namespace lamd;
 
@@ -1648,6 +1649,7 @@ struct lamd_ctx {
   int q_open = 0;                 // the set being filled, -1 when every set is in flight
   int q_fifo[QUEUE_SETS] = {0};   // flushed sets, oldest first
   int q_inflight = 0;
+  size_t last_flush_inplace_rows = 0;   // rows the last successful lamd_flush sent from the callers' registered memory (lamd_info)
   // Lanes: the device-pointer entry points rotate over LAMD_LANES (default 6) complete sub-contexts (own streams and
   // workspaces, the G table shared), so that the latency-bound front end of one call (key de-duplication, the count
   // read-back, table building) runs under the VALU-bound ecmult kernels of the calls before it.  A lane's `peer` is the
@@ -2221,6 +2223,7 @@ static int get_info_of(lamd_ctx *ctx, lamd_info *info) {
   info->gtable_bytes = GTABLE_BYTES;
   info->hw_queues_env = hw_queues_from_env();
   info->queue_sets = QUEUE_SETS;
+  info->last_flush_inplace_rows = root->last_flush_inplace_rows;
   for (int i = 0; i < 4; i++) info->last_kernel_ms[i] = ctx->last_ms[i];
   for (int i = 0; i < 2; i++) {
     info->keyed_ecmult_ms_sum[i] = self->keyed_ms_sum[i];
@@ -3902,8 +3905,9 @@ extern "C" int lamd_queue_schnorr_batch(lamd_ctx *ctx, size_t n, const uint8_t *
 // The rows stay where they are: n triples in the caller's memory (keys packed, publen bytes each) get a row range in the open staging set and cross
 // the bus FROM THE CALLER'S BUFFERS when the set is flushed -- the form for a host that already holds its callers' rows in pinned memory (lamd_served:
 // the clients' shared blocks, registered with lamd_host_register()).  The buffers must not change until the flush that carries the rows has been
-// collected (lamd_poll / lamd_wait).  Batches the latency kernel would take (<= 4 096 rows), and rows in memory the runtime does not hold pinned,
-// are copied like lamd_queue_*_batch().
+// collected (lamd_poll / lamd_wait).  Batches the latency kernel would take (<= 4 096 rows), and rows that do not lie inside ONE range registered
+// through lamd_host_register(), are copied like lamd_queue_*_batch().
+static lamd::host_ranges g_registered;   // the ranges lamd_host_register() pinned (portable: the process's, for every device and context)
 static int queue_push_inplace(lamd_ctx *ctx, int kind, size_t n, const u8 *a, const u8 *sig, const u8 *key) {
   if (!ctx) return LAMD_ERR_ARG;
   if (!a || !sig || !key) {
@@ -3913,18 +3917,13 @@ static int queue_push_inplace(lamd_ctx *ctx, int kind, size_t n, const u8 *a, co
   if (n <= SMALL_MAX || !ctx->use_copy_stream) return queue_push(ctx, kind, n, a, sig, key, Q_KEYBYTES[kind]);
   // Only memory the runtime holds pinned stays in place.  An asynchronous copy from PAGEABLE memory makes the runtime pin the pages itself for the
   // length of the transfer, and such a transient pin next to (in one page with) a registered range left the runtime unable to finish a later
-  // pageable copy (tests: a process hung in an unrelated device-to-host copy, round 6) -- so rows in memory that is not registered end to end are
-  // copied into the staging set like any others.
+  // pageable copy (tests: a process hung in an unrelated device-to-host copy, round 6) -- so a column stays in place only if it lies inside one
+  // range registered through lamd_host_register(); a column that spans two registrations, has a pageable hole, or lies in memory pinned by other
+  // means is copied into the staging set like any other.
   const size_t w[3] = {32, 64, Q_KEYBYTES[kind]};
   const u8 *col[3] = {a, sig, key};
   for (int c = 0; c < 3; c++)
-    for (const u8 *p : {col[c], col[c] + w[c] * n - 1}) {
-      hipPointerAttribute_t at;
-      if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return queue_push(ctx, kind, n, a, sig, key, Q_KEYBYTES[kind]);
-      }
-    }
+    if (!g_registered.covers(col[c], w[c] * n)) return queue_push(ctx, kind, n, a, sig, key, Q_KEYBYTES[kind]);
   u8 *da, *db, *dc;
   const int first = queue_take(ctx, kind, n, &da, &db, &dc);
   if (first < 0) return first;
@@ -3951,6 +3950,7 @@ extern "C" int lamd_host_register(lamd_ctx *ctx, void *p, size_t bytes) {
     (void)hipGetLastError();
     return LAMD_ERR_HIP;
   }
+  g_registered.add(p, bytes);
   return LAMD_OK;
 }
 // The NUMA node a device hangs on (/sys/bus/pci/devices/<domain:bus:device.function>/numa_node), -1 when the platform does not say: where a host puts the
@@ -3972,6 +3972,7 @@ extern "C" int lamd_device_numa_node(int device) {
 }
 extern "C" int lamd_host_unregister(lamd_ctx *ctx, void *p) {
   if (!ctx || !p) return LAMD_ERR_ARG;
+  g_registered.remove(p);   // first: from now on no column in it is queued in place, whatever the runtime answers
   if (hipSetDevice(ctx->device) != hipSuccess || hipHostUnregister(p) != hipSuccess) {
     (void)hipGetLastError();
     return LAMD_ERR_HIP;
@@ -3979,13 +3980,35 @@ extern "C" int lamd_host_unregister(lamd_ctx *ctx, void *p) {
   return LAMD_OK;
 }
 // Launches everything queued so far as one batch per kind (asynchronous, on the next lane) and opens the next staging set:
-// queueing continues while up to QUEUE_SETS - 1 flushes are in flight.
+// queueing continues while up to QUEUE_SETS - 1 flushes are in flight.  A flush that fails drops the open set (flush_open may have queued copies
+// and kernels of some kinds before a later one failed): the device is drained first, so that nothing reads the callers' in-place rows or the set's
+// buffers any more once the error is returned, then the set's rows, tickets and in-place spans are forgotten -- the next flush carries only
+// what is queued after this one.
+static int flush_open(lamd_ctx *ctx);
 extern "C" int lamd_flush(lamd_ctx *ctx) {
   if (!ctx) return LAMD_ERR_ARG;
   if (ctx->q_open < 0) {
     ctx->err = "flush: every staging set is in flight (collect a flush with poll/wait first)";
     return LAMD_ERR_STATE;
   }
+  const int rc = flush_open(ctx);
+  if (rc < 0 && ctx->q_open >= 0) {
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    lamd_ctx::queue_set &qs = ctx->qs[ctx->q_open];
+    for (int kind = 0; kind < Q_KINDS; kind++) {
+      lamd_ctx::queue &q = qs.q[kind];
+      q.tickets.clear();
+      q.foreign.clear();
+      q.n = 0;
+      q.small_flush = false;
+    }
+    qs.rows = 0;
+    ctx->last_flush_inplace_rows = 0;
+  }
+  return rc;
+}
+static int flush_open(lamd_ctx *ctx) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   lamd_ctx::queue_set &qs = ctx->qs[ctx->q_open];
   lamd_ctx *L;
@@ -4180,6 +4203,10 @@ extern "C" int lamd_flush(lamd_ctx *ctx) {
   } else {
     HIPCHK(ctx, hipEventRecord(qs.done, L->stream));
   }
+  size_t inplace = 0;
+  for (int kind = 0; kind < Q_KINDS; kind++)
+    for (const auto &f : qs.q[kind].foreign) inplace += f.count;
+  ctx->last_flush_inplace_rows = inplace;
   ctx->q_fifo[ctx->q_inflight++] = ctx->q_open;
   // the next set to fill: any set that is not in flight
   ctx->q_open = -1;

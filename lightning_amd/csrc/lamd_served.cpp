@@ -66,6 +66,7 @@ struct engine_api {
   decltype(&lamd_host_register) host_register = nullptr;
   decltype(&lamd_host_unregister) host_unregister = nullptr;
   decltype(&lamd_device_numa_node) numa_node = nullptr;   // optional
+  decltype(&lamd_get_info) get_info = nullptr;            // optional (queue_sets: how many engine flushes may be in flight)
   decltype(&lamd_flush) flush = nullptr;
   decltype(&lamd_poll) poll = nullptr;
   decltype(&lamd_wait) wait = nullptr;
@@ -102,6 +103,7 @@ struct job {
   // request runs, and an offset re-read after the check could point anywhere
   std::vector<uint64_t> o_in, o_out, o_sc;
   size_t queued_rows = 0;  // flush: rows that reached the engine's staging set
+  bool failed = false;     // flush: this part has its error (a queue call or the engine flush failed) -- never answered OK
 };
 
 // one engine context = one GPU = one engine thread
@@ -145,7 +147,9 @@ bool g_inplace = true;
 // Every device's engine thread -- and the thread that creates its context, while it does -- runs on the CPUs of the NUMA node the device hangs on: the
 // context's pinned staging sets are first touched there and the launches come from the near socket.  --no-numa leaves the threads where the scheduler puts them.
 bool g_numa = true;
-const size_t ENGINE_FLUSHES_IN_FLIGHT = 8;
+// engine flushes in flight per device.  Rows are queued while that many are out, so the engine needs one staging set more: main() clamps this to the
+// engine's lamd_info.queue_sets - 1 (a queue call that finds every set in flight fails with LAMD_ERR_STATE)
+size_t g_flights = 8;
 
 const uint8_t *sec(const job *j, int i) { return j->c->shm[j->slot].p + j->off[i]; }
 size_t seclen(const job *j, int i) { return (size_t)j->req.section_len[i]; }
@@ -166,6 +170,11 @@ void fail(job *j, int rc, const char *why) {
 void engine_error(job *j, int rc) {
   j->rep.rc = rc;
   if (rc < 0) snprintf(j->rep.err, sizeof j->rep.err, "%s", E.last_error(g_ctx));
+}
+// a flush part fails: whatever the engine returned (LAMD_ERR_STATE included), it stays an error
+void flush_error(job *j, int rc) {
+  engine_error(j, rc < 0 ? rc : LAMD_ERR_STATE);
+  j->failed = true;
 }
 // input sections present with exactly these lengths, and `out_bytes` of output fit behind them
 bool shape(job *j, std::initializer_list<size_t> lens, size_t out_bytes) {
@@ -467,14 +476,17 @@ bool collect_one(bool block) {
   if (rc == 0) return false;
   size_t o = 0;
   for (job *j : f.parts) {
-    if (j->rep.rc == LAMD_ERR_STATE) {  // not failed while it was queued
-      if (rc == 1 && n == f.rows) {
+    // OK only for a part that failed nowhere and had EVERY row in this engine flush, whose verdict count is the one queued; anything else is an
+    // error (its verdict region stays zero: submit_flushes cleared it)
+    if (!j->failed) {
+      if (rc == 1 && n == f.rows && j->queued_rows == (size_t)j->req.n) {
         memcpy(outp(j, 0), &D->okbuf[o], j->queued_rows);
         j->rep.rc = LAMD_OK;
       } else if (rc < 0) {
-        engine_error(j, rc);
+        flush_error(j, rc);
       } else {
-        fail(j, LAMD_ERR_STATE, "engine flush returned another number of verdicts than were queued");
+        fail(j, LAMD_ERR_STATE, n != f.rows ? "engine flush returned another number of verdicts than were queued" : "flush part not queued whole");
+        j->failed = true;
       }
     }
     o += j->queued_rows;
@@ -489,15 +501,16 @@ void submit_flushes(std::vector<job *> &fl) {
   auto launch = [&]() {
     if (cur.parts.empty()) return;
     if (cur.rows) {
-      while (D->inflight.size() >= ENGINE_FLUSHES_IN_FLIGHT) collect_one(true);
+      while (D->inflight.size() >= g_flights) collect_one(true);
       const int rc = E.flush(g_ctx);
       stat_add(&g_stats.engine_flushes, 1);
       stat_max(&g_stats.largest_engine_flush_requests, cur.parts.size());
       stat_add(&g_stats.rows_by_device[D->id], cur.rows);
-      if (rc < 0)
+      if (rc < 0) {
+        // a failed flush has dropped the open set (include/lightning_amd.h): the engine finished or abandoned whatever it had started reading from the
+        // blocks before it returned, and none of these rows is read again -- so the parts may be answered (and their blocks reused) now
         for (job *j : cur.parts)
-          if (j->rep.rc == LAMD_ERR_STATE) engine_error(j, rc);
-      if (rc < 0) {  // nothing went to the device: answer now
+          if (!j->failed) flush_error(j, rc);
         for (job *j : cur.parts) answer_async(j);
         cur = flight();
         return;
@@ -512,6 +525,7 @@ void submit_flushes(std::vector<job *> &fl) {
     stat_add(&g_stats.flushes, 1);
     if (!flush_valid(j)) { answer_async(j); continue; }
     const size_t n = (size_t)j->req.n;
+    memset(outp(j, 0), 0, n);  // the verdicts of the block's previous flush are never read as this one's (flush_valid: the region lies in the block)
     stat_add(&g_stats.flush_rows, n);
     if (cur.rows && cur.rows + n > g_max_flush_rows) launch();
     size_t o = 0, ko = 0;
@@ -526,7 +540,7 @@ void submit_flushes(std::vector<job *> &fl) {
                                 : E.queue_ecdsa(g_ctx, cnt, sec(j, 1) + 32 * o, sec(j, 2) + 64 * o, sec(j, 3) + ko, kl, kl);
       if (rc >= 0 && inplace) stat_add(&g_stats.flush_rows_in_place, cnt);
       if (rc < 0) {  // the rows queued so far stay in the set (their verdicts are dropped); this client gets the error
-        engine_error(j, rc);
+        flush_error(j, rc);
         break;
       }
       j->queued_rows += cnt;
@@ -814,6 +828,7 @@ int main(int argc, char **argv) {
   *(void **)&E.host_register = dlsym(E.lib, "lamd_host_register");
   *(void **)&E.host_unregister = dlsym(E.lib, "lamd_host_unregister");
   *(void **)&E.numa_node = dlsym(E.lib, "lamd_device_numa_node");
+  *(void **)&E.get_info = dlsym(E.lib, "lamd_get_info");
   memset(&g_stats, 0, sizeof g_stats);
   for (size_t k = 0; k < devices.size(); k++) {
     device *dev = new device;
@@ -836,6 +851,15 @@ int main(int argc, char **argv) {
       return 1;  // no engine, no service: there is no CPU verification to fall back to
     }
     g_dev.push_back(dev);
+    lamd_info info;
+    if (E.get_info && E.get_info(dev->ctx, &info) == LAMD_OK) {  // rows are queued with g_flights flushes out: one staging set more than that
+      if (info.queue_sets < 2) {
+        fprintf(stderr, "lamd_served: the engine of device %d has %d staging set(s); streaming needs two\n", devices[k], info.queue_sets);
+        for (device *d : g_dev) E.shutdown(d->ctx);
+        return 1;
+      }
+      if ((size_t)info.queue_sets - 1 < g_flights) g_flights = (size_t)info.queue_sets - 1;
+    }
   }
   g_stats.devices = g_dev.size();
   auto shutdown_all = [] { for (device *d : g_dev) E.shutdown(d->ctx); };

@@ -8,22 +8,34 @@
 
 #include <pthread.h>
 
-#define STUB_SETS 16
+#define STUB_SETS 16     /* the most staging sets STUB_QUEUE_SETS may ask for (and the default) */
 #define STUB_DEFERRED 64
 /* rows queued in place: their verdicts are computed when the flush is COLLECTED, from the caller's buffers -- a host that lets go of (or rewrites) a
  * buffer before it has collected the flush gets the wrong verdicts here */
 struct stub_deferred { size_t pos, n, publen; const uint8_t *a, *b, *c; };
-struct stub_set { uint8_t *ok; size_t n, cap; int polled; struct stub_deferred late[STUB_DEFERRED]; int n_late; };
-struct lamd_ctx { int device; unsigned long calls, rows, largest, inplace_rows; char err[64]; struct stub_set open, closed[STUB_SETS]; int head, count; };
+/* fail_flush / miscount: a poisoned queue call asked for this set's lamd_flush to fail part-way, for its collection to report a wrong count */
+struct stub_set { uint8_t *ok; size_t n, cap; int polled; struct stub_deferred late[STUB_DEFERRED]; int n_late; int fail_flush, miscount; };
+struct lamd_ctx { int device, sets; unsigned long calls, rows, largest, inplace_rows; char err[64]; struct stub_set open, closed[STUB_SETS]; int head, count; };
 
 int lamd_init(lamd_ctx **ctx, int device) {
+	const char *sets = getenv("STUB_QUEUE_SETS");
 	*ctx = calloc(1, sizeof **ctx);
 	(*ctx)->device = device;
+	(*ctx)->sets = sets && atoi(sets) >= 1 && atoi(sets) <= STUB_SETS ? atoi(sets) : STUB_SETS;
 	if (device == 99) { strcpy((*ctx)->err, "stub: no such device"); return LAMD_ERR_NO_DEVICE; }
 	return LAMD_OK;
 }
 void lamd_shutdown(lamd_ctx *ctx) { free(ctx); }
 const char *lamd_last_error(const lamd_ctx *ctx) { return ctx->err; }
+int lamd_get_info(lamd_ctx *ctx, lamd_info *info) {
+	if (!ctx || !info) return LAMD_ERR_ARG;
+	memset(info, 0, sizeof *info);
+	info->device = ctx->device;
+	strcpy(info->arch, "stub");
+	info->lanes = 1;
+	info->queue_sets = ctx->sets;
+	return LAMD_OK;
+}
 static void note(lamd_ctx *c, size_t n) { c->calls++; c->rows += n; if (n > c->largest) c->largest = n; }
 
 int lamd_verify_ecdsa_batch(lamd_ctx *ctx, size_t n, const uint8_t *h, const uint8_t *s, const uint8_t *p, size_t publen, size_t stride, uint8_t *ok) {
@@ -129,7 +141,14 @@ int lamd_grind_htlc_tx_fee(lamd_ctx *ctx, const uint8_t *preimage, size_t preima
 
 /* ---- the streaming queue (include/lightning_amd.h "streaming"): the open set collects verdict bytes in ticket order, lamd_flush closes it,
  * lamd_poll / lamd_wait hand the OLDEST closed set back.  Verdicts are the functions of the synchronous calls above; lamd_poll reports the
- * oldest flush "still running" once (the server must come back for it), as a busy engine would. */
+ * oldest flush "still running" once (the server must come back for it), as a busy engine would.
+ * STUB_QUEUE_SETS=k (1..16, default 16): k staging sets as in the engine -- with all k flushed and not collected there is no open set, and every
+ * lamd_queue_* call and lamd_flush returns LAMD_ERR_STATE.
+ * Poison markers: the first row of a queue call whose hash / message begins 0xEE and then
+ *   0xEE  the call fails with LAMD_ERR_HIP (ECDSA only; nothing is queued)
+ *   0x5E  the call fails with LAMD_ERR_STATE, as the engine's queue_take does when the set is full (nothing is queued)
+ *   0xF1  the rows are queued, but the lamd_flush that carries them fails after part of the set was "sent": it drops the open set (the contract)
+ *   0xC7  the rows are queued, but the collection of their flush reports one verdict fewer than the flush carried */
 #define g_open (ctx->open)
 #define g_closed (ctx->closed)
 #define g_head (ctx->head)
@@ -138,15 +157,28 @@ static void push_ok(lamd_ctx *ctx, uint8_t v) {
 	if (g_open.n == g_open.cap) { g_open.cap = g_open.cap ? 2 * g_open.cap : 1024; g_open.ok = realloc(g_open.ok, g_open.cap); }
 	g_open.ok[g_open.n++] = v;
 }
+/* < 0: the queue call fails with that code before a row is queued; 0: go on (a marker may have flagged the open set) */
+static int poisoned(lamd_ctx *ctx, size_t n, const uint8_t *a, int ecdsa) {
+	if (ctx->count == ctx->sets) { strcpy(ctx->err, "stub: every staging set is in flight"); return LAMD_ERR_STATE; }
+	if (!n || a[0] != 0xEE) return 0;
+	switch (a[1]) {
+	case 0xEE: if (ecdsa) { strcpy(ctx->err, "stub: poisoned batch"); return LAMD_ERR_HIP; } break;
+	case 0x5E: strcpy(ctx->err, "stub: staging set full"); return LAMD_ERR_STATE;
+	case 0xF1: g_open.fail_flush = 1; break;
+	case 0xC7: g_open.miscount = 1; break;
+	}
+	return 0;
+}
 int lamd_queue_ecdsa_batch(lamd_ctx *ctx, size_t n, const uint8_t *h, const uint8_t *s, const uint8_t *p, size_t publen, size_t stride) {
-	const int first = (int)g_open.n;
-	if (n && h[0] == 0xEE && h[1] == 0xEE) { strcpy(ctx->err, "stub: poisoned batch"); return LAMD_ERR_HIP; }
+	const int first = (int)g_open.n, bad = poisoned(ctx, n, h, 1);
+	if (bad < 0) return bad;
 	for (size_t i = 0; i < n; i++) push_ok(ctx, (h[32 * i] ^ s[64 * i + 63] ^ p[stride * i + publen - 1]) & 1);
 	ctx->rows += n;
 	return first;
 }
 int lamd_queue_schnorr_batch(lamd_ctx *ctx, size_t n, const uint8_t *m, const uint8_t *x, const uint8_t *s) {
-	const int first = (int)g_open.n;
+	const int first = (int)g_open.n, bad = poisoned(ctx, n, m, 0);
+	if (bad < 0) return bad;
 	for (size_t i = 0; i < n; i++) push_ok(ctx, (m[32 * i + 1] ^ x[32 * i + 2] ^ s[64 * i + 3]) & 1);
 	ctx->rows += n;
 	return first;
@@ -184,7 +216,8 @@ static int registered(const uint8_t *p, size_t bytes) {
 	return ok;
 }
 static int push_late(lamd_ctx *ctx, size_t n, const uint8_t *a, const uint8_t *b, const uint8_t *c, size_t alen, size_t blen, size_t clen, size_t publen) {
-	const int first = (int)g_open.n;
+	const int first = (int)g_open.n, bad = poisoned(ctx, n, a, publen != 0);
+	if (bad < 0) return bad;
 	if (!registered(a, alen * n) || !registered(b, blen * n) || !registered(c, clen * n)) { strcpy(ctx->err, "stub: in-place rows outside registered memory"); return LAMD_ERR_ARG; }
 	if (g_open.n_late == STUB_DEFERRED) { strcpy(ctx->err, "stub: too many in-place batches in one set"); return LAMD_ERR_STATE; }
 	g_open.late[g_open.n_late++] = (struct stub_deferred){g_open.n, n, publen, a, b, c};
@@ -194,7 +227,6 @@ static int push_late(lamd_ctx *ctx, size_t n, const uint8_t *a, const uint8_t *b
 	return first;
 }
 int lamd_queue_ecdsa_batch_inplace(lamd_ctx *ctx, size_t n, const uint8_t *h, const uint8_t *s, const uint8_t *p, size_t publen) {
-	if (n && h[0] == 0xEE && h[1] == 0xEE) { strcpy(ctx->err, "stub: poisoned batch"); return LAMD_ERR_HIP; }
 	return push_late(ctx, n, h, s, p, 32, 64, publen, publen);
 }
 int lamd_queue_schnorr_batch_inplace(lamd_ctx *ctx, size_t n, const uint8_t *m, const uint8_t *x, const uint8_t *s) {
@@ -202,8 +234,14 @@ int lamd_queue_schnorr_batch_inplace(lamd_ctx *ctx, size_t n, const uint8_t *m, 
 }
 int lamd_device_numa_node(int device) { return device == 2 ? -1 : 0; }   /* (device 2: a platform that does not say) */
 int lamd_flush(lamd_ctx *ctx) {
+	if (g_count == ctx->sets) { strcpy(ctx->err, "stub: too many flushes outstanding"); return LAMD_ERR_STATE; }
 	if (!g_open.n) return LAMD_OK;
-	if (g_count == STUB_SETS) { strcpy(ctx->err, "stub: too many flushes outstanding"); return LAMD_ERR_STATE; }
+	if (g_open.fail_flush) {  /* the contract: a failed flush drops the rows queued since the previous one (in-place rows are never read again) */
+		free(g_open.ok);
+		memset(&g_open, 0, sizeof g_open);
+		strcpy(ctx->err, "stub: flush failed part-way");
+		return LAMD_ERR_HIP;
+	}
 	g_closed[(g_head + g_count++) % STUB_SETS] = g_open;
 	memset(&g_open, 0, sizeof g_open);
 	note(ctx, 0);
@@ -218,7 +256,7 @@ static int take(lamd_ctx *ctx, uint8_t *ok, size_t cap, size_t *n) {
 							       : (d->a[32 * i + 1] ^ d->b[32 * i + 2] ^ d->c[64 * i + 3]) & 1;
 	}
 	memcpy(ok, g_closed[g_head].ok, g_closed[g_head].n);
-	*n = g_closed[g_head].n;
+	*n = g_closed[g_head].n - (g_closed[g_head].miscount && g_closed[g_head].n);
 	free(g_closed[g_head].ok);
 	memset(&g_closed[g_head], 0, sizeof g_closed[0]);
 	g_head = (g_head + 1) % STUB_SETS;

@@ -1054,6 +1054,111 @@ def test_streaming_rows_queued_in_place(eng, orc):
         eng.queue_ecdsa_batch_inplace(hs[:, :31], sg, pk)
 
 
+def _registered_block(eng, x, regs):
+    """x copied into pages of its own, registered (lamd_host_register) -- recorded in regs for host_unregister"""
+    a = _page_block(x)
+    assert eng.host_register(a), "hipHostRegister refused whole pages of host memory"
+    regs.append(a)
+    return a
+
+
+def test_streaming_in_place_rows_across_chunk_boundaries(eng, orc):
+    """the in-place branch of lamd_flush with more rows in a kind than one chunk (set_chunk_rows 4 096 instead of 2^22): in-place runs
+    that begin and end inside chunks and straddle one to three chunk boundaries, copied runs before, between and after them, three kinds, three
+    flushes in flight -- verdicts equal the oracle's row for row, and lamd_info.last_flush_inplace_rows shows that the in-place rows crossed the bus
+    from the caller's registered pages (not copied into the staging set)"""
+    rnd = random.Random(6161)
+    P33, P65, PS = 16000, 9600, 7600
+    hs, sg, pk = _random_ecdsa(orc, rnd, P33, 33)
+    e33 = orc.ecdsa_verify_batch(hs, sg, pk, 33, 8).astype(bool)
+    hs65, sg65, pk65 = _random_ecdsa(orc, rnd, P65, 65)
+    e65 = orc.ecdsa_verify_batch(hs65, sg65, pk65, 65, 8).astype(bool)
+    ms, xs, ss, es = _random_schnorr(orc, rnd, PS)
+    assert (~e33).sum() > P33 // 10 and (~es).sum() > PS // 10
+
+    def pool(cols, exp, shift, n):        # n rows of a pool, starting at `shift` (wrapping): -> (columns, verdicts)
+        idx = (np.arange(n) + shift) % len(exp)
+        return [np.ascontiguousarray(c[idx]) for c in cols], exp[idx]
+
+    eng.set_chunk_rows(4096)
+    outstanding, regs_of = [], []
+    try:
+        for f in range(5):
+            regs, exp, inplace = [], [], 0
+            # ECDSA-33: copied | in place (straddles 2-3 chunk boundaries) | copied | in place (1-2) | copied
+            lay33 = [(300 + 17 * f, False), (9000 + 613 * f, True), (77, False), (5000 - 211 * f, True), (123 + f, False)]
+            # ECDSA-65: copied | in place (1-2 boundaries) | copied;  BIP-340: copied | in place (1-2) | copied
+            lay65 = [(50 + 31 * f, False), (8500 - 397 * f, True), (20, False)]
+            lays = [(6 * f + 1, False), (6000 + 401 * f, True), (5, False)]
+            ticket = 0
+            for kind, lay, cols, vexp in (("e33", lay33, (hs, sg, pk), e33), ("sch", lays, (ms, xs, ss), es), ("e65", lay65, (hs65, sg65, pk65), e65)):
+                at = 1000 * f
+                for n, inp in lay:
+                    c, v = pool(cols, vexp, at, n)
+                    at += n
+                    if inp:
+                        c = [_registered_block(eng, x, regs) for x in c]
+                        inplace += n
+                    if kind == "sch":
+                        t = (eng.queue_schnorr_batch_inplace if inp else eng.queue_schnorr_batch)(*c)
+                    else:
+                        t = (eng.queue_ecdsa_batch_inplace if inp else eng.queue_ecdsa_batch)(*c)
+                    assert t == ticket, (f, kind, t, ticket)
+                    ticket += n
+                    exp.append(v)
+            eng.flush()
+            moved = eng.info()["last_flush_inplace_rows"]
+            assert moved == inplace, (f, moved, inplace)
+            outstanding.append((np.concatenate(exp), f, regs))
+            if len(outstanding) == 3:
+                e, ff, rr = outstanding.pop(0)
+                got = eng.wait()
+                assert np.array_equal(got, e), (ff, np.nonzero(got != e)[0][:10])
+                assert all(eng.host_unregister(x) for x in rr)
+        while outstanding:
+            e, ff, rr = outstanding.pop(0)
+            got = eng.wait()
+            assert np.array_equal(got, e), (ff, np.nonzero(got != e)[0][:10])
+            assert all(eng.host_unregister(x) for x in rr)
+    finally:
+        eng.set_chunk_rows(0)
+
+
+def test_in_place_column_over_two_registrations_is_copied(eng, orc):
+    """a column that lies in two ADJACENT registered blocks -- pinned end to end, but by no single registration -- is copied into the staging set
+    (lamd_info.last_flush_inplace_rows 0) and verifies like any other; the same rows in one registered block each stay in place"""
+    import mmap
+    rnd = random.Random(7171)
+    n = 5000
+    hs, sg, pk = _random_ecdsa(orc, rnd, n, 33)
+    exp = orc.ecdsa_verify_batch(hs, sg, pk, 33, 8).astype(bool)
+    pg = mmap.PAGESIZE
+    half = (32 * n // 2 + pg - 1) // pg * pg                          # each block holds about half of the hash column
+    m = mmap.mmap(-1, 2 * half)
+    whole = np.frombuffer(m, dtype=np.uint8)
+    lo, hi = whole[:half], whole[half:]
+    regs = []
+    assert eng.host_register(lo) and eng.host_register(hi), "hipHostRegister refused whole pages of host memory"
+    try:
+        start = half - 32 * (n // 2)                                    # the column's seam between the blocks falls after row n // 2
+        col = whole[start:start + 32 * n].reshape(n, 32)
+        col[:] = hs
+        s2, k2 = _registered_block(eng, sg, regs), _registered_block(eng, pk, regs)
+        assert eng.queue_ecdsa_batch_inplace(col, s2, k2) == 0
+        eng.flush()
+        assert eng.info()["last_flush_inplace_rows"] == 0
+        got = eng.wait()
+        assert np.array_equal(got, exp), np.nonzero(got != exp)[0][:10]
+        h1 = _registered_block(eng, hs, regs)
+        assert eng.queue_ecdsa_batch_inplace(h1, s2, k2) == 0
+        eng.flush()
+        assert eng.info()["last_flush_inplace_rows"] == n
+        got = eng.wait()
+        assert np.array_equal(got, exp), np.nonzero(got != exp)[0][:10]
+    finally:
+        assert all(eng.host_unregister(x) for x in regs + [lo, hi])
+
+
 def test_key_table_cache_warm_cold_and_bounded(orc):
     """the key-table cache: a second call over the same keys builds no table and verifies every row from cached combs (same
     verdicts); keys that do not parse are cached as such; a cache too small for the traffic empties itself and carries on;
