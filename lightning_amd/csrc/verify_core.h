@@ -98,12 +98,6 @@ constexpr int SLOT_WORDS = LAMD_TABLE_LIMBS ? 288 : 256;             // scratch 
 #ifndef LAMD_GTABLE_WINDOW_BITS
 #define LAMD_GTABLE_WINDOW_BITS 24
 #endif
-#ifndef LAMD_G_RUN_XYZZ
-#define LAMD_G_RUN_XYZZ 1
-#endif
-#ifndef LAMD_UNROLL_HALF
-#define LAMD_UNROLL_HALF 0
-#endif
 constexpr int GTABLE_WINDOW_BITS = LAMD_GTABLE_WINDOW_BITS;
 constexpr int GTABLE_WINDOWS = (256 + GTABLE_WINDOW_BITS - 1) / GTABLE_WINDOW_BITS;
 constexpr size_t GTABLE_ENTRIES = (size_t)GTABLE_WINDOWS << GTABLE_WINDOW_BITS;
@@ -863,25 +857,15 @@ LAMD_HD comb_pair<T> comb_from_rec_odd(const prep_rec &rec) {
 // accumulator (no infinity handling), every addition is the bare formula (gej_add_ge_fast) and the G windows skip a zero
 // digit by branching.  Degenerate events (an addition meeting +-its operand: adversarial scalars only, or the result being
 // infinity) leave Z = 0, which the caller tests ONCE: *suspect = true means "verdict unknown, run ecmult_lane_keyed".
-// (glds: experiment only, -DLAMD_G_LDS -- the north star's "LDS-staged precomputed G table": 52 windows x 32 entries x 64 B = 104 KB
-// staged into the block's LDS by the kernel; u1*G then takes 52 additions from LDS instead of 12 from the 3 GiB table in HBM.
-// Measured A/B in profiles/r03_ab_variants.txt; the shipped build has no such code.)
-constexpr int GLDS_BITS = 5, GLDS_WINDOWS = (256 + GLDS_BITS - 1) / GLDS_BITS, GLDS_WORDS = GLDS_WINDOWS * (1 << GLDS_BITS) * 16;
 template <int T>
-LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u32 *gtable, bool *suspect, const u32 *glds = nullptr) {
+LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u32 *gtable, bool *suspect) {
   constexpr int D = kc_spacing(T), NE = kc_ne(T);
   const comb_pair<T> cp = comb_from_rec_odd<T>(rec);
   gej acc = gej_infinity();
 #pragma unroll 1
   for (int j = D - 1; j >= 0; j--) {
     if (j != D - 1) acc = gej_double(acc);
-    // (-DLAMD_UNROLL_HALF=1, an experiment: both additions of a column as straight-line code -- the accumulator's 27 registers are copied at
-    // the column loop's back edge only, not after every addition; 12 KB more code.  profiles/r06_ab_variants.txt)
-#if LAMD_UNROLL_HALF
-#pragma unroll
-#else
 #pragma unroll 1
-#endif
     for (int half = 0; half < 2; half++) {
       u32 m = 0;
 #pragma unroll
@@ -893,20 +877,6 @@ LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u
       pt.x = slot_load_fe(e + (half ? ENT_BX : ENT_X));
       pt.y = slot_load_fe(e + ENT_Y);
       pt = ge_neg_if_lazy(pt, top == (half ? cp.n2 : cp.n1));
-#if defined(LAMD_TOUCH_NEXT) && defined(__HIP_DEVICE_COMPILE__)
-      // experiment (not in the shipped build): touch the table entry of the NEXT addition before this one starts, so that its cache
-      // lines are on their way from HBM while the ~1000 multiply-adds of this addition issue.  One dword per coordinate, result unused.
-      if (half == 0 || j > 0) {
-        const int nj = half ? j - 1 : j, nh = half ? 0 : 1;
-        u32 nm = 0;
-#pragma unroll
-        for (int i = 0; i < T; i++) nm |= (((nh ? cp.tooth2[i] : cp.tooth1[i]) >> nj) & 1u) << i;
-        const u32 nidx = (((nm >> (T - 1)) & 1u) ? nm : ~nm) & (u32)(NE - 1);
-        const volatile u32 *ne_ = tab + nidx * SLOT_ENTRY_WORDS;
-        (void)ne_[nh ? ENT_BX : ENT_X];
-        (void)ne_[ENT_Y];
-      }
-#endif
       if (j == D - 1 && half == 0) {  // uniform across the wave: the first point is the accumulator
         acc.x = pt.x;
         acc.y = fe_norm_weak(pt.y);
@@ -922,34 +892,8 @@ LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u
   u32 uw[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) uw[i] = rec.u1[i];
-#if defined(LAMD_G_LDS)
-  if (glds) {
-#pragma unroll 1
-    for (int w = 0; w < GLDS_WINDOWS; w++) {
-      const u32 d = uw[0] & ((1u << GLDS_BITS) - 1u);
-#pragma unroll
-      for (int i = 0; i < 7; i++) uw[i] = (uw[i] >> GLDS_BITS) | (uw[i + 1] << (32 - GLDS_BITS));
-      uw[7] >>= GLDS_BITS;
-      if (d != 0) {
-        const u32 *e = glds + ((w << GLDS_BITS) + d) * 16;
-        u32 xw[8], yw[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) { xw[i] = e[i]; yw[i] = e[8 + i]; }
-        ge pt;
-        pt.x = fe_from_words(xw);
-        pt.y = fe_from_words(yw);
-        acc = gej_add_ge_fast(acc, pt);
-      }
-    }
-    *suspect = fe_is_zero(acc.z);
-    return gexz_from_gej(acc);
-  }
-#endif
   // the G windows are a run of additions without a doubling: XYZZ coordinates (group.h), a squaring less per addition
-  // (-DLAMD_G_RUN_XYZZ=0: the Jacobian run of rounds 1-5, converted at the end -- the A/B in profiles/r06_ab_variants.txt)
-#if LAMD_G_RUN_XYZZ
   gexz xz = gexz_from_gej(acc);
-#endif
 #pragma unroll 1
   for (int w = 0; w < GTABLE_WINDOWS; w++) {
     const u32 d = uw[0] & ((1u << GTABLE_WINDOW_BITS) - 1u);
@@ -957,26 +901,13 @@ LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u
     for (int i = 0; i < 7; i++) uw[i] = (uw[i] >> GTABLE_WINDOW_BITS) | (uw[i + 1] << (32 - GTABLE_WINDOW_BITS));
     uw[7] >>= GTABLE_WINDOW_BITS;
     if (d != 0) {  // a zero digit (2^-22 per window) is a divergent skip, not a select
-#if defined(LAMD_CLOCK_PROBE_G_HOT)
-      // clock experiment (profiles/r06_clock.txt; verdicts are WRONG in this build): every window reads from the first 64 MiB of the table --
-      // the same eleven additions and loads, served from the Infinity Cache instead of HBM
-      const u32 *e = gtable + (size_t)(d & 0xFFFFFu) * GT_ENTRY_WORDS;
-#else
       const u32 *e = gtable + (((size_t)w << GTABLE_WINDOW_BITS) + d) * GT_ENTRY_WORDS;
-#endif
       ge pt;
       pt.x = slot_load_fe(e);
       pt.y = slot_load_fe(e + TW);
-#if LAMD_G_RUN_XYZZ
       xz = gexz_add_ge_fast(xz, pt);
-#else
-      acc = gej_add_ge_fast(acc, pt);
-#endif
     }
   }
-#if !LAMD_G_RUN_XYZZ
-  const gexz xz = gexz_from_gej(acc);
-#endif
   *suspect = fe_is_zero(xz.zz);
   return xz;
 }
@@ -1321,22 +1252,9 @@ LAMD_HD gej pairs_sum_row(const prep_rec &rec, const u32 *tab, const u32 *gtable
 // table, false when row b has no work (past the end of the list, scalars that failed the preparation); `first` tells the pass-1
 // call from the pass-2 call.  done(b, R, suspect): the row's result; suspect as ecmult_lane_keyed_fast (R is garbage then).
 // ws: the lane's PAIRS_SLOTS parking slots, ws_stride words apart.
-#if defined(LAMD_PAIRS_CLOCK) && defined(__HIPCC__)
-// experiment build: where a lane's time goes (pass 1 | inversion | pass 2), summed over all lanes in 100 MHz ticks (tools/pairs_clock_probe.py)
-__device__ unsigned long long g_pairs_clk[8];   // [0..2] phase sums | [3] max lane total | [4] min start | [5] max end | [6] max pass 1 | [7] max pass 2
-#endif
-#if defined(LAMD_PAIRS_CLOCK) && defined(__HIP_DEVICE_COMPILE__)
-#define LAMD_PCLK(k) do { const unsigned long long now_ = wall_clock64(); atomicAdd(&g_pairs_clk[k], now_ - pclk_); if ((k) == 0) atomicMax(&g_pairs_clk[6], now_ - pclk_); \
-    if ((k) == 2) { atomicMax(&g_pairs_clk[7], now_ - pclk_); atomicMax(&g_pairs_clk[3], now_ - pclk0_); atomicMax(&g_pairs_clk[5], now_); } pclk_ = now_; } while (0)
-#define LAMD_PCLK_START unsigned long long pclk_ = wall_clock64(); const unsigned long long pclk0_ = pclk_; atomicMin(&g_pairs_clk[4], pclk_);
-#else
-#define LAMD_PCLK(k) ((void)0)
-#define LAMD_PCLK_START
-#endif
 template <int T, class RowF, class DoneF>
 LAMD_HD void pairs_batch(int nb, const u32 *gtable, u32 *ws, size_t ws_stride, RowF row, DoneF done) {
   constexpr int NP = pairs_per_row(T);
-  LAMD_PCLK_START
   fe P = fe_set_int(1);
   pairs_ws_store(ws, P);
   u32 good = 0;
@@ -1357,9 +1275,7 @@ LAMD_HD void pairs_batch(int nb, const u32 *gtable, u32 *ws, size_t ws_stride, R
     ng++;
   }
   if (ng == 0) return;
-  LAMD_PCLK(0);
   fe inv = fe_inv_var(P);
-  LAMD_PCLK(1);
 #pragma unroll 1
   for (int b = nb - 1; b >= 0; b--) {
     if (!((good >> b) & 1u)) continue;
@@ -1371,7 +1287,6 @@ LAMD_HD void pairs_batch(int nb, const u32 *gtable, u32 *ws, size_t ws_stride, R
     const gej R = pairs_sum_row<T>(*rec, tab, gtable, inv, ws + (size_t)(1 + ng * NP) * ws_stride, ws_stride, &suspect);
     done(b, R, suspect);
   }
-  LAMD_PCLK(2);
 }
 
 // ================================================================================================

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A few isolated calls (synchronised in between) for per-kernel durations under `rocprofv3 --kernel-trace --stats`.
-usage: [LAMD_CACHE=0] [LAMD_KEYED_WAVES=3] python tools/prof_calls.py [rows]"""
+usage: [LAMD_CACHE=0] python tools/prof_calls.py [rows]"""
 import os
 import sys
 
