@@ -256,6 +256,78 @@ int lamd_sigcheck_gossip_batch_device(lamd_ctx *ctx, size_t n, const void *d_msg
 int lamd_sigcheck_gossip_spans_device(lamd_ctx *ctx, size_t n, const void *d_msgs, const void *d_start, const void *d_len,
 				      const void *d_node_ids33, const void *d_rowbase, size_t rows, void *d_verdict);
 
+/* ---- audit of a gossip_store FILE: every live record's checksum and every signature in it, before the daemon trusts the file.
+ * The reference's start-up load (gossmap_load_initial -> map_catchup, common/gossmap.c:815-937) checks framing, flags and the CRC-32C of
+ * each live record (csum_matches, :799-812) and never looks at a signature again (gossipd/gossmap_manage.c:508-539): a store copied from
+ * another node, fetched as a snapshot, or damaged in a way that keeps the CRCs valid is loaded as it stands.  Here the checksums, the look-up
+ * of every channel_update's signer in the store itself (the channel_announcement of its short_channel_id, node_id_1 / node_id_2 by the
+ * direction bit: what gossmap_manage.c:920-922 asks the gossmap) and all signatures are one device call.
+ *
+ * The walk over the records is sequential, runs on the host and reads headers only (struct gossip_hdr, common/gossip_store.h:44-49, and
+ * the 2-byte type).  It follows map_catchup: starts at offset 1 and stops -- lamd_store_summary.end_reason, end_offset -- when fewer than
+ * 12 bytes are left, at a record without the COMPLETED flag, at one that reaches past the end of the file, at a live one shorter than 2
+ * bytes, BEHIND a gossip_store_ended record (4105; the reference reopens the new file, here it is reported), and at a live
+ * channel_announcement that is not followed by room for its channel_amount record (gossmap.c:488-492).  A file whose major version (top
+ * three bits of byte 0) is not 0 is refused with LAMD_ERR_ARG.
+ *
+ * verdict[i] of record i, the first that applies:
+ *    8  LAMD_STORE_SKIPPED_DELETED  DELETED flag set: nothing checked (gossmap.c:844-847)
+ *   -2  LAMD_STORE_BAD_CHECKSUM     crc32c(timestamp, msg, len) != hdr.crc (:870-888, gossip_store.c:67)
+ *   -4  LAMD_STORE_UNKNOWN_TYPE     not 256 / 257 / 258 / 4101 / 4103 / 4105 / 4106 / 4107 (:918-925; the obsolete 4102 / 4104 included)
+ *   -1  LAMD_STORE_MALFORMED        what lamd_sigcheck_gossip_batch calls -1
+ *   -5  LAMD_STORE_REDUNDANT        a live channel_announcement of this scid exists at a lower offset (gossmap.c:475-486)
+ *   -3  LAMD_STORE_NO_CHANNEL       channel_update without a live channel_announcement of its scid at a lower offset (update_channel
+ *                                   false, :898-899), or whose announcement is cut off before the node id
+ *  1..4                             the first bad signature, numbered as lamd_sigcheck_gossip_batch numbers them
+ *    0  LAMD_STORE_OK               checksum good; for the three gossip kinds every signature good
+ * Verdicts of different records are independent except for the signer look-up: an update is judged against the node ids of its
+ * announcement whatever that announcement's own verdict.  Live or dead is decided by the FLAGS ALONE: gossipd itself marks what a
+ * delete_chan tombstone (4103) removes as DELETED (gossip_store.c:622-638), so tombstones are checksummed and counted, never applied.
+ * Records 4101 / 4106 / 4107 get the checksum only; following store_ended into the new file, dying deadlines, the upgrade of old versions
+ * and the legacy 0x4000 push bit of version 15 (ignored) are left to the reference's own load. */
+enum {
+	LAMD_STORE_OK = 0,
+	LAMD_STORE_MALFORMED = -1,
+	LAMD_STORE_BAD_CHECKSUM = -2,
+	LAMD_STORE_NO_CHANNEL = -3,
+	LAMD_STORE_UNKNOWN_TYPE = -4,
+	LAMD_STORE_REDUNDANT = -5,
+	LAMD_STORE_SKIPPED_DELETED = 8
+};
+enum {
+	LAMD_STORE_END_EOF = 0,            /* the walk consumed the file to its last byte */
+	LAMD_STORE_END_PARTIAL_HEADER = 1, /* 1..11 bytes left */
+	LAMD_STORE_END_INCOMPLETE = 2,     /* a record without the COMPLETED flag */
+	LAMD_STORE_END_TRUNCATED = 3,      /* a record reaches past the end of the file */
+	LAMD_STORE_END_SHORT = 4,          /* a live record of fewer than 2 bytes */
+	LAMD_STORE_END_STORE_ENDED = 5,    /* a gossip_store_ended record: counted, the walk stops behind it */
+	LAMD_STORE_END_NO_AMOUNT = 6       /* a live channel_announcement without room for its channel_amount record: not counted */
+};
+typedef struct {
+	int version;              /* byte 0 of the file */
+	int end_reason;           /* LAMD_STORE_END_* */
+	int clean;                /* 1 iff end_reason is LAMD_STORE_END_EOF and every verdict is OK or SKIPPED_DELETED (always 0 from lamd_gossip_store_frame) */
+	uint64_t records, live, deleted;
+	uint64_t end_offset;      /* where the walk stopped */
+	/* one counter per verdict code, summed from the verdict array (all 0 from lamd_gossip_store_frame) */
+	uint64_t ok, skipped_deleted, bad_checksum, unknown_type, malformed, redundant, no_channel;
+	uint64_t bad_signature[4]; /* verdicts 1..4 */
+	uint64_t signatures;      /* signature rows verified: 4 per live channel_announcement, 1 per live node_announcement / channel_update */
+	double stage_ms[5];       /* with lamd_set_timing(ctx, 1): device time of checksums, index, signers, signatures, verdicts (HIP events); else 0 */
+} lamd_store_summary;
+/* host only, no context: the walk.  rec_off[i] = offset of record i's gossip_hdr (cap entries; may be NULL with cap == 0).  cap too small:
+ * LAMD_ERR_ARG with *n_records = the count needed and the summary filled. */
+int lamd_gossip_store_frame(const uint8_t *store, size_t len, size_t cap, uint64_t *rec_off, size_t *n_records, lamd_store_summary *summary);
+/* the audit.  d_store == NULL: `store` is copied to the device; otherwise the image is already resident at d_store (len bytes) and `store`
+ * (host) is read for the 12 bytes of header + 2 of type per record only.  rec_off / verdict: cap entries each (call lamd_gossip_store_frame
+ * first to size them; cap too small: LAMD_ERR_ARG with *n_records = the count needed).  The device work is queued without any host
+ * synchronisation between its stages -- CRC-32C of every live record (k_store_crc), scid index of the live announcements (k_store_index),
+ * signers and redundancy (k_store_signers), ONE signature batch over the live 256 / 257 / 258 records (the spans form of
+ * lamd_sigcheck_gossip_spans_device), the merge (k_store_verdict) -- and ends with one copy of the verdict bytes; the call returns when
+ * they have arrived.  A store holding only its version byte is LAMD_OK with clean = 1. */
+int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off,
+			    int8_t *verdict, size_t *n_records, lamd_store_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

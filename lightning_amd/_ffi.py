@@ -26,6 +26,14 @@ class LamdInfo(ctypes.Structure):
                 ("last_flush_inplace_rows", ctypes.c_size_t)]
 
 
+class LamdStoreSummary(ctypes.Structure):
+    """lamd_store_summary (include/lightning_amd.h): what lamd_gossip_store_frame / lamd_gossip_store_audit report about a gossip_store file"""
+    _fields_ = [("version", ctypes.c_int), ("end_reason", ctypes.c_int), ("clean", ctypes.c_int), ("records", ctypes.c_uint64), ("live", ctypes.c_uint64),
+                ("deleted", ctypes.c_uint64), ("end_offset", ctypes.c_uint64), ("ok", ctypes.c_uint64), ("skipped_deleted", ctypes.c_uint64),
+                ("bad_checksum", ctypes.c_uint64), ("unknown_type", ctypes.c_uint64), ("malformed", ctypes.c_uint64), ("redundant", ctypes.c_uint64),
+                ("no_channel", ctypes.c_uint64), ("bad_signature", ctypes.c_uint64 * 4), ("signatures", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 5)]
+
+
 # name -> (restype, argtypes); every symbol of include/lightning_amd.h and include/lightning_amd_debug.h
 SYMBOLS = {
     "lamd_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
@@ -63,6 +71,8 @@ SYMBOLS = {
     "lamd_wait": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.POINTER(c_sz)]),
     "lamd_sigcheck_gossip_batch_device": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_sz, c_u8p]),
     "lamd_sigcheck_gossip_spans_device": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_sz, c_u8p]),
+    "lamd_gossip_store_frame": (ctypes.c_int, [c_u8p, c_sz, c_sz, c_u8p, ctypes.POINTER(c_sz), ctypes.POINTER(LamdStoreSummary)]),
+    "lamd_gossip_store_audit": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.POINTER(c_sz), ctypes.POINTER(LamdStoreSummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

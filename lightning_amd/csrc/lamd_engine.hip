@@ -20,6 +20,7 @@
 #include "verify_core.h"
 #include "fuzz.h"
 #include "host_ranges.h"
+#include "store_audit.h"
 
 using namespace lamd;
 
@@ -450,6 +451,49 @@ __global__ void __launch_bounds__(256) k_gossip_reduce(size_t n, const u8 *__res
   if (i >= n) return;
   const size_t row = rowbase[i];
   verdict[i] = (int8_t)gossip_reduce_one(rowbase[i + 1] - row, ok + row, keyok + row, malformed[i]);
+}
+
+// ---- gossip_store audit (lamd_gossip_store_audit; per-record logic in store_audit.h).  One lane per record throughout.
+// k_store_crc: the block builds the slicing tables in LDS (thread t computes entry t of table 0 from the bitwise definition; every further
+// table reads table 0 only), then each lane checksums its record -- bytes until the pointer is 4-aligned, 32-bit loads, tail bytes -- and
+// classifies it.  A lane's cost is its record's length: gossip records are 130-450 bytes, the 65 535-byte maximum is correct, not fast.
+template <int WAYS>
+__global__ void __launch_bounds__(256) k_store_crc(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                   int8_t *__restrict__ pre) {
+  __shared__ u32 T[WAYS * 256];
+  const u32 t = threadIdx.x;
+  u32 v = store_crc_t0(t);
+  T[t] = v;
+  __syncthreads();
+  for (int k = 1; k < WAYS; k++) {
+    v = (v >> 8) ^ T[v & 0xff];
+    T[256 * k + t] = v;
+  }
+  __syncthreads();
+  const u32 i = blockIdx.x * 256 + t;
+  if (i < n) pre[i] = (int8_t)store_precheck_one<WAYS>(T, store, store_len, rec_off[i]);
+}
+// keys / vals: (1 << bits) + 1 slots, preset to all-ones bytes (STORE_EMPTY_KEY / STORE_NONE)
+__global__ void __launch_bounds__(256) k_store_index(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                     u64 *keys, u32 *vals, u32 bits) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_index_one(store, store_len, rec_off[i], i, keys, vals, bits);
+}
+// sel[i] = the record's row in the signature selection (STORE_NONE: it has none): a channel_update's signer goes to ids33 + 33 * sel[i]
+__global__ void __launch_bounds__(256) k_store_signers(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                       const u32 *__restrict__ sel, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
+                                                       u32 bits, u8 *__restrict__ ids33, u8 *__restrict__ aux) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const u32 j = sel[i];
+  aux[i] = (u8)store_signer_one(store, store_len, rec_off, i, keys, vals, bits, j != STORE_NONE ? ids33 + 33 * (size_t)j : nullptr);
+}
+__global__ void __launch_bounds__(256) k_store_verdict(u32 n, const int8_t *__restrict__ pre, const u32 *__restrict__ sel,
+                                                       const int8_t *__restrict__ sigv, const u8 *__restrict__ aux, int8_t *__restrict__ verdict) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const u32 j = sel[i];
+  verdict[i] = (int8_t)store_merge_one(pre[i], j != STORE_NONE, j != STORE_NONE ? sigv[j] : 0, aux[i]);
 }
 
 // (the synthetic-workload signer kernels live in lamd_testgen.hip -> liblightning_amd_testgen.so: test / bench infrastructure,
@@ -1562,6 +1606,8 @@ struct lamd_ctx {
   bool last_keyed_call = false;
   devbuf in_a, in_b, in_c, out;       // staging for the host-buffer API
   devbuf g_msgs, g_off, g_ids, g_rowbase, g_hash, g_sig, g_pub, g_malformed, g_ok, g_verdict;
+  devbuf st_img, st_host, st_ids, st_tab, st_out;   // gossip_store audit: image, the host walk's arrays, signers, scid index, per-record bytes
+  hipEvent_t ev_store[6] = {};                      // ... and its stage boundaries (created when a timed audit first runs)
   // timing
   bool timing = false;
   bool ev_recorded = false;
@@ -1943,8 +1989,10 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
   for (devbuf *b : {&ctx->small_done, &ctx->recs, &ctx->qwords, &ctx->keyok, &ctx->slots, &ctx->vbuf, &ctx->in_a, &ctx->in_b, &ctx->in_c, &ctx->out,
                     &ctx->g_msgs, &ctx->g_off, &ctx->g_ids, &ctx->g_rowbase, &ctx->g_hash, &ctx->g_sig, &ctx->g_pub,
-                    &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict})
+                    &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict, &ctx->st_img, &ctx->st_host, &ctx->st_ids, &ctx->st_tab, &ctx->st_out})
     release(b);
+  for (auto &e : ctx->ev_store)
+    if (e) (void)hipEventDestroy(e);
   for (auto &qs : ctx->qs) {
     for (auto &q : qs.q) {
       q.h_a = q.h_b = q.h_c = nullptr;
@@ -3627,6 +3675,145 @@ extern "C" int lamd_sigcheck_gossip_spans_device(lamd_ctx *ctx, size_t n, const 
                      (const u64 *)d_len);
   if (rc != LAMD_OK && L != ctx) ctx->err = L->err;
   return rc;
+}
+
+// ---- gossip_store audit
+static void store_count_verdicts(const int8_t *v, size_t n, lamd_store_summary *s) {
+  for (size_t i = 0; i < n; i++) {
+    switch (v[i]) {
+      case LAMD_STORE_OK: s->ok++; break;
+      case LAMD_STORE_SKIPPED_DELETED: s->skipped_deleted++; break;
+      case LAMD_STORE_BAD_CHECKSUM: s->bad_checksum++; break;
+      case LAMD_STORE_UNKNOWN_TYPE: s->unknown_type++; break;
+      case LAMD_STORE_MALFORMED: s->malformed++; break;
+      case LAMD_STORE_REDUNDANT: s->redundant++; break;
+      case LAMD_STORE_NO_CHANNEL: s->no_channel++; break;
+      default:
+        if (v[i] >= 1 && v[i] <= 4) s->bad_signature[v[i] - 1]++;
+    }
+  }
+  s->clean = s->end_reason == LAMD_STORE_END_EOF && s->ok + s->skipped_deleted == n;
+}
+extern "C" int lamd_gossip_store_frame(const uint8_t *store, size_t len, size_t cap, uint64_t *rec_off, size_t *n_records,
+                                       lamd_store_summary *summary) {
+  if (!store || !n_records || !summary || (cap && !rec_off)) return LAMD_ERR_ARG;
+  *n_records = 0;
+  if (!store_walk(store, len, summary, [&](size_t i, u64 off, const store_hdr &, u32) {
+        if (i < cap) rec_off[i] = off;
+      }))
+    return LAMD_ERR_ARG;
+  *n_records = (size_t)summary->records;
+  return summary->records > cap ? LAMD_ERR_ARG : LAMD_OK;
+}
+// Everything between the host walk and the final copy is queued on one lane's stream: image (unless resident) and the walk's arrays up,
+// four kernels and the signature batch, the verdict bytes down.
+extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off,
+                                       int8_t *verdict, size_t *n_records, lamd_store_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!store || !n_records || !summary || (cap && (!rec_off || !verdict))) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  *n_records = 0;
+  // the walk: record offsets, and the selection of the signature batch -- the live 256 / 257 / 258 records (4 rows / 1 / 1)
+  std::vector<u64> start, mlen, rowbase;
+  std::vector<u32> sel;
+  size_t n_cann = 0;
+  u64 rows = 0;
+  if (!store_walk(store, len, summary, [&](size_t i, u64 off, const store_hdr &h, u32 type) {
+        if (i < cap) rec_off[i] = off;
+        const bool sig = type == STORE_T_CANN || type == STORE_T_NANN || type == STORE_T_CUPD;
+        sel.push_back(sig ? (u32)start.size() : STORE_NONE);
+        if (!sig) return;
+        start.push_back(off + STORE_HDR);
+        mlen.push_back(h.len);
+        rowbase.push_back(rows);
+        rows += type == STORE_T_CANN ? 4 : 1;
+        n_cann += type == STORE_T_CANN;
+      })) {
+    ctx->err = "not a gossip_store of major version 0";
+    return LAMD_ERR_ARG;
+  }
+  const size_t n = (size_t)summary->records, nsel = start.size();
+  *n_records = n;
+  if (n > cap) { ctx->err = "gossip_store audit: rec_off / verdict too small"; return LAMD_ERR_ARG; }
+  if (n >= (size_t)STORE_NONE || rows >= (u64)STORE_NONE) { ctx->err = "gossip_store audit: too many records"; return LAMD_ERR_ARG; }
+  summary->signatures = rows;
+  if (n == 0) { store_count_verdicts(verdict, 0, summary); return LAMD_OK; }
+  rowbase.push_back(rows);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  lamd_ctx *L;
+  int rc = pick_lane(ctx, &L);
+  if (rc != LAMD_OK) return rc;
+  u32 bits = 1;
+  while (((size_t)1 << bits) < 2 * n_cann) bits++;
+  const size_t slots = ((size_t)1 << bits) + 1;
+  // host arrays, one copy: rec_off u64[n] | start u64[nsel] | len u64[nsel] | rowbase u64[nsel + 1] | sel u32[n]
+  std::vector<u64> pack(n + 3 * nsel + 1 + (n + 1) / 2);
+  for (size_t i = 0; i < n; i++) pack[i] = rec_off[i];
+  if (nsel) {
+    memcpy(&pack[n], start.data(), 8 * nsel);
+    memcpy(&pack[n + nsel], mlen.data(), 8 * nsel);
+  }
+  memcpy(&pack[n + 2 * nsel], rowbase.data(), 8 * (nsel + 1));
+  memcpy(&pack[n + 3 * nsel + 1], sel.data(), 4 * n);
+  auto fail = [&](int code) {   // queued copies read this frame's vectors
+    (void)hipStreamSynchronize(L->stream);
+    if (L != ctx) ctx->err = L->err;
+    return code;
+  };
+  if ((rc = ensure(L, &L->st_host, pack.size() * 8)) != LAMD_OK) return fail(rc);
+  if ((rc = ensure(L, &L->st_ids, nsel * 33 + 16)) != LAMD_OK) return fail(rc);
+  if ((rc = ensure(L, &L->st_tab, slots * 12)) != LAMD_OK) return fail(rc);
+  if ((rc = ensure(L, &L->st_out, 3 * n + nsel + 16)) != LAMD_OK) return fail(rc);
+  if (!d_store && (rc = ensure(L, &L->st_img, len + 16)) != LAMD_OK) return fail(rc);
+  const bool timed = ctx->timing;
+  if (timed)
+    for (auto &e : L->ev_store)
+      if (!e) HIPCHK(ctx, hipEventCreate(&e));
+  hipStream_t st = L->stream;
+  const u64 *d_pack = L->st_host.as<const u64>();
+  const u64 *d_recoff = d_pack, *d_start = d_pack + n, *d_len = d_start + nsel, *d_rowbase = d_len + nsel;
+  const u32 *d_sel = (const u32 *)(d_rowbase + nsel + 1);
+  u64 *d_keys = L->st_tab.as<u64>();
+  u32 *d_vals = (u32 *)(d_keys + slots);
+  int8_t *d_pre = L->st_out.as<int8_t>(), *d_verdict = d_pre + n, *d_sigv = d_verdict + n;
+  u8 *d_aux = (u8 *)(d_sigv + nsel);
+  const u8 *img = (const u8 *)d_store;
+#define STCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { L->err = std::string(#call) + ": " + hipGetErrorString(e_); return fail(LAMD_ERR_HIP); } } while (0)
+  if (!d_store) {
+    STCHK(hipMemcpyAsync(L->st_img.p, store, len, hipMemcpyHostToDevice, st));
+    img = L->st_img.as<const u8>();
+  }
+  STCHK(hipMemcpyAsync(L->st_host.p, pack.data(), pack.size() * 8, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(L->st_tab.p, 0xFF, slots * 12, st));
+  // slicing by 8 measured faster (0.24 ms against 0.42 ms on 750 000 records, profiles/store_audit.txt): LAMD_STORE_CRC_WAYS=8 selects it.  The
+  // default stays the variant the GPU tests have run with until they have run with the other one.
+  static const int crc_ways = [] { const char *e = getenv("LAMD_STORE_CRC_WAYS"); return e && atoi(e) == 8 ? 8 : 4; }();
+  const dim3 grid(blocks_for(n)), block(256);
+  if (timed) STCHK(hipEventRecord(L->ev_store[0], st));
+  if (crc_ways == 8) hipLaunchKernelGGL(k_store_crc<8>, grid, block, 0, st, (u32)n, img, len, d_recoff, d_pre);
+  else hipLaunchKernelGGL(k_store_crc<4>, grid, block, 0, st, (u32)n, img, len, d_recoff, d_pre);
+  if (timed) STCHK(hipEventRecord(L->ev_store[1], st));
+  hipLaunchKernelGGL(k_store_index, grid, block, 0, st, (u32)n, img, len, d_recoff, d_keys, d_vals, bits);
+  if (timed) STCHK(hipEventRecord(L->ev_store[2], st));
+  hipLaunchKernelGGL(k_store_signers, grid, block, 0, st, (u32)n, img, len, d_recoff, d_sel, (const u64 *)d_keys, (const u32 *)d_vals, bits,
+                     L->st_ids.as<u8>(), d_aux);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(L->ev_store[3], st));
+  if (nsel && (rc = gossip_device(L, nsel, img, d_start, L->st_ids.as<const u8>(), d_rowbase, (size_t)rows, d_sigv, d_len)) != LAMD_OK) return fail(rc);
+  if (timed) STCHK(hipEventRecord(L->ev_store[4], st));
+  hipLaunchKernelGGL(k_store_verdict, grid, block, 0, st, (u32)n, (const int8_t *)d_pre, d_sel, (const int8_t *)d_sigv, (const u8 *)d_aux, d_verdict);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(L->ev_store[5], st));
+  STCHK(hipMemcpyAsync(verdict, d_verdict, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed)
+    for (int k = 0; k < 5; k++) {
+      float ms = 0;
+      STCHK(hipEventElapsedTime(&ms, L->ev_store[k], L->ev_store[k + 1]));
+      summary->stage_ms[k] = ms;
+    }
+#undef STCHK
+  store_count_verdicts(verdict, n, summary);
+  return LAMD_OK;
 }
 
 extern "C" int lamd_sigcheck_gossip_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *off,

@@ -23,6 +23,37 @@ def _u8(a, shape_tail):
     return a
 
 
+STORE_END_REASONS = ("eof", "partial_header", "incomplete", "truncated", "short", "store_ended", "no_amount")   # LAMD_STORE_END_*
+
+
+def _store_summary(s):
+    d = {k: int(getattr(s, k)) for k in ("version", "clean", "records", "live", "deleted", "end_offset", "ok", "skipped_deleted", "bad_checksum", "unknown_type",
+                                         "malformed", "redundant", "no_channel", "signatures")}
+    d.update(end_reason=STORE_END_REASONS[s.end_reason], bad_signature=[int(x) for x in s.bad_signature], stage_ms=list(s.stage_ms))
+    return d
+
+
+def _store_blob(blob):
+    a = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, dtype=np.uint8)
+    return a, a.size, (a if a.size else np.zeros(1, dtype=np.uint8))
+
+
+def gossip_store_frame(blob):
+    """lamd_gossip_store_frame: the walk over a gossip_store image (bytes or numpy uint8), on the host, no context.
+    -> (rec_off uint64 [records], summary dict)"""
+    lib = _ffi.load()
+    _, n_bytes, buf = _store_blob(blob)
+    n, s = ctypes.c_size_t(0), _ffi.LamdStoreSummary()
+    rc = lib.lamd_gossip_store_frame(buf.ctypes.data, n_bytes, 0, None, ctypes.byref(n), ctypes.byref(s))
+    if rc < 0 and n.value == 0:
+        raise LamdError("lamd_gossip_store_frame: %s" % ERRORS.get(rc, rc))
+    off = np.zeros(max(1, n.value), dtype=np.uint64)
+    rc = lib.lamd_gossip_store_frame(buf.ctypes.data, n_bytes, n.value, off.ctypes.data, ctypes.byref(n), ctypes.byref(s))
+    if rc < 0:
+        raise LamdError("lamd_gossip_store_frame: %s" % ERRORS.get(rc, rc))
+    return off[:n.value], _store_summary(s)
+
+
 class Engine:
     """One context = one GPU, one stream.  Mirrors lamd_init()/lamd_shutdown()."""
 
@@ -252,6 +283,25 @@ class Engine:
         verdict = np.zeros(n, dtype=np.int8)
         self._chk(self._lib.lamd_sigcheck_gossip_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, ids_ptr, verdict.ctypes.data))
         return verdict
+
+    def gossip_store_audit(self, blob, d_store=None):
+        """lamd_gossip_store_audit over a gossip_store image (bytes or numpy uint8): checksums and every signature, on the device.
+        d_store: the same image resident in a torch uint8 CUDA tensor (it is then not copied).
+        -> (rec_off uint64 [records], verdict int8 [records], summary dict)"""
+        _, n_bytes, buf = _store_blob(blob)
+        cnt, s = ctypes.c_size_t(0), _ffi.LamdStoreSummary()
+        self._lib.lamd_gossip_store_frame(buf.ctypes.data, n_bytes, 0, None, ctypes.byref(cnt), ctypes.byref(s))   # the count; the audit reports every error itself
+        n = cnt.value
+        off, verdict = np.zeros(max(1, n), dtype=np.uint64), np.zeros(max(1, n), dtype=np.int8)
+        d_ptr = None
+        if d_store is not None:
+            if d_store.numel() != n_bytes:
+                raise ValueError("the resident image and the host image differ in size")
+            self._after_torch()
+            d_ptr = d_store.data_ptr()
+        self._chk(self._lib.lamd_gossip_store_audit(self._ctx, buf.ctypes.data, n_bytes, d_ptr, n, off.ctypes.data, verdict.ctypes.data, ctypes.byref(cnt),
+                                                    ctypes.byref(s)))
+        return off[:cnt.value], verdict[:cnt.value], _store_summary(s)
 
     # ---- single-item veneers (reference semantics)
     def check_signed_hash(self, hash32, sig64, pubkey):

@@ -1,0 +1,113 @@
+"""Measures lamd_gossip_store_audit on one MI355X (not part of bench.py): a synthetic gossip_store built on the device-generated cfg4
+traffic (lightning_amd/workload.py make_gossip: channel_announcements + their channel_amount records + channel_updates), framed on the
+host with valid CRCs; the time of every stage from HIP events (checksums, index, signers, signatures, verdicts) and of the whole call,
+against lamd_sigcheck_gossip_spans_device over the same messages with host-supplied signers.  The slicing variant of k_store_crc is
+chosen per process: run once with --ways 4 and once with --ways 8.
+
+    python tools/store_audit_bench.py --ways 8 [--cann 150000 --cupd 450000 --runs 10]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--ways", type=int, default=4, choices=(4, 8))
+ap.add_argument("--cann", type=int, default=150_000)
+ap.add_argument("--cupd", type=int, default=450_000)
+ap.add_argument("--runs", type=int, default=10)
+args = ap.parse_args()
+os.environ["LAMD_STORE_CRC_WAYS"] = str(args.ways)     # read once, at the first audit of the process
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from lightning_amd import Engine  # noqa: E402
+from lightning_amd.workload import CANN_LEN, CUPD_LEN, make_gossip  # noqa: E402
+
+
+def crc32c_rows(seed, rows):
+    """crc32c(seed[i], rows[i]) for equally long rows, one table step per byte column"""
+    t = np.arange(256, dtype=np.uint32)
+    for _ in range(8):
+        t = np.where(t & 1, (t >> 1) ^ np.uint32(0x82F63B78), t >> 1)
+    c = ~seed.astype(np.uint32)
+    for k in range(rows.shape[1]):
+        c = t[(c ^ rows[:, k]) & 0xFF] ^ (c >> 8)
+    return ~c
+
+
+def records(msgs, ts):
+    """[n, len] messages -> [n, 12 + len] store records (COMPLETED, crc32c seeded with the timestamp)"""
+    n, ln = msgs.shape
+    out = np.zeros((n, 12 + ln), dtype=np.uint8)
+    out[:, 0] = 0x20
+    out[:, 2], out[:, 3] = ln >> 8, ln & 0xFF
+    crc = crc32c_rows(ts, msgs)
+    for k in range(4):
+        out[:, 4 + k] = (crc >> (24 - 8 * k)) & 0xFF
+        out[:, 8 + k] = (ts >> (24 - 8 * k)) & 0xFF
+    out[:, 12:] = msgs
+    return out
+
+
+def spread(xs):
+    xs = sorted(xs)
+    return dict(min=round(xs[0], 3), median=round(xs[len(xs) // 2], 3), max=round(xs[-1], 3))
+
+
+with Engine(0) as eng:
+    w = make_gossip(eng, args.cann, args.cupd)
+    cann = w.msgs[:args.cann * CANN_LEN].reshape(args.cann, CANN_LEN)
+    cupd = w.msgs[args.cann * CANN_LEN:args.cann * CANN_LEN + args.cupd * CUPD_LEN].reshape(args.cupd, CUPD_LEN)
+    amount = np.zeros((args.cann, 10), dtype=np.uint8)
+    amount[:, 0], amount[:, 1], amount[:, 7] = 0x10, 0x05, 1
+    ts_a, ts_u = np.arange(args.cann, dtype=np.uint32) + 1_600_000_000, np.arange(args.cupd, dtype=np.uint32) + 1_650_000_000
+    pairs = np.concatenate([records(cann, ts_a), records(amount, np.zeros(args.cann, dtype=np.uint32))], axis=1)
+    image = np.concatenate([np.array([0x10], dtype=np.uint8), pairs.reshape(-1), records(cupd, ts_u).reshape(-1)])
+    d_image = torch.from_numpy(image).cuda()
+    # the same messages as a spans call with host-supplied signers: the baseline
+    a_rec, u_rec = 12 + CANN_LEN + 22, 12 + CUPD_LEN
+    start = np.concatenate([1 + 12 + a_rec * np.arange(args.cann, dtype=np.int64), 1 + a_rec * args.cann + 12 + u_rec * np.arange(args.cupd, dtype=np.int64)])
+    length = np.concatenate([np.full(args.cann, CANN_LEN, dtype=np.int64), np.full(args.cupd, CUPD_LEN, dtype=np.int64)])
+    d_start, d_len = torch.from_numpy(start).cuda(), torch.from_numpy(length).cuda()
+    torch.cuda.synchronize()
+
+    def spans():
+        t0 = time.perf_counter()
+        eng.sigcheck_gossip_spans_device(w.n, d_image, d_start, d_len, w.d_ids, w.d_rowbase, w.rows, w.d_verdict)
+        eng.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def audit(resident):
+        t0 = time.perf_counter()
+        out = eng.gossip_store_audit(image, d_store=d_image if resident else None)
+        return (time.perf_counter() - t0) * 1e3, out
+
+    spans()
+    assert np.array_equal(w.d_verdict.cpu().numpy(), w.expect), "baseline verdicts differ from the generator's"
+    _, (off, verdict, s) = audit(True)
+    v = verdict.astype(np.int64)
+    assert s["records"] == 2 * args.cann + args.cupd and s["end_reason"] == "eof" and s["signatures"] == w.rows
+    assert np.array_equal(v[0:2 * args.cann:2], w.expect[:args.cann]) and not v[1:2 * args.cann:2].any() and np.array_equal(v[2 * args.cann:], w.expect[args.cann:]), \
+        "audit verdicts differ from the generator's"
+    base = [spans() for _ in range(args.runs)]
+    eng.set_timing(True)
+    res, stages = [], []
+    for _ in range(args.runs):
+        ms, (_, _, s) = audit(True)
+        res.append(ms)
+        stages.append(s["stage_ms"])
+    eng.set_timing(False)
+    res_untimed = [audit(True)[0] for _ in range(args.runs)]
+    host = [audit(False)[0] for _ in range(3)]
+    names = ("crc", "index", "signers", "signatures", "verdict")
+    print(json.dumps(dict(
+        crc_ways=args.ways, records=s["records"], signatures=s["signatures"], image_bytes=int(image.size), runs=args.runs,
+        spans_call_ms=spread(base), audit_resident_call_ms=spread(res_untimed), audit_resident_call_timed_ms=spread(res), audit_host_image_call_ms=spread(host),
+        stage_ms={n: spread([st[k] for st in stages]) for k, n in enumerate(names)},
+        new_stages_ms=spread([st[0] + st[1] + st[2] + st[4] for st in stages]),
+        signature_stage_spread_ms=round(max(st[3] for st in stages) - min(st[3] for st in stages), 3))))
