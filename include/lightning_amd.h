@@ -328,6 +328,54 @@ int lamd_gossip_store_frame(const uint8_t *store, size_t len, size_t cap, uint64
 int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off,
 			    int8_t *verdict, size_t *n_records, lamd_store_summary *summary);
 
+/* ---- repair of a gossip_store FILE: the audit, and behind it, on the device, the store that holds what passed.
+ * The reference's load stops at the first bad checksum (common/gossmap.c:870-888) and never checks a signature; its only rewriting tool,
+ * gossipd/compactd.c, copies every record that is not flagged deleted (and is not a uuid or delete_chan record), whatever it holds.  Here
+ * the rewritten store holds the records whose verdict is OK and whose dependencies are kept, in file order, behind a fresh uuid record.
+ *
+ * Record i is KEPT iff it is live (DELETED flag clear), verdict[i] == LAMD_STORE_OK, and, by its type ("indexed" = the lowest-index live
+ * channel_announcement of that short_channel_id, as the audit's scid index returns it):
+ *    256 channel_announcement  record i+1 exists, is live, is of type 4101 and length 10 and has verdict OK: gossmap reads the amount
+ *                              from the record that follows without checking what it is (gossmap.c:488-492)
+ *   4101 channel_amount        record i-1 is a kept 256
+ *    258 channel_update        the indexed announcement of its scid has a lower record index and is kept
+ *   4106 chan_dying            its length is 14, and the indexed announcement of its scid has a lower record index and is kept
+ *    257 node_announcement     its node_id equals node_id_1 or node_id_2 of a kept channel_announcement with a lower record index
+ *   4103 delete_chan, 4107 uuid, 4105 store_ended   never kept (compactd's first phase drops the first two; the walk stops behind the third)
+ *   anything else              never kept
+ * reason[i], why record i is not in the output:
+ *   0  kept
+ *   1  DELETED flag set
+ *   2  the record itself: verdict[i] is neither OK nor NO_CHANNEL (or a chan_dying record is not 14 bytes long)
+ *   3  a dependency: its announcement is dropped or missing (verdict NO_CHANNEL included), its amount record is missing or not OK, its
+ *      node is in no kept announcement with a lower index
+ *   4  store bookkeeping: 4103 / 4105 / 4107
+ * for a live record the first of 2, 4, 3 that applies.
+ *
+ * The output: the input's version byte; one uuid record built from uuid32 (flags COMPLETED, timestamp 0, type 4107, crc32c seeded with 0:
+ * 46 bytes); the kept records, headers verbatim (the DYING flag bit with them), in file order.  It is never longer than len + 46 bytes.
+ * new_off[i] = offset of record i's gossip_hdr in the output, UINT64_MAX for a dropped record: the map gossmap_manage needs when it
+ * swaps files. */
+typedef struct {
+	uint64_t kept;
+	/* one counter per reason 1..4 */
+	uint64_t dropped_deleted, dropped_verdict, dropped_dependency, dropped_bookkeeping;
+	uint64_t out_len;         /* length of the rewritten store */
+	double stage_ms[3];       /* with lamd_set_timing(ctx, 1): device time of keep flags, scan, copy (HIP events); else 0 */
+} lamd_store_repair_summary;
+/* store / len / d_store / cap / rec_off / verdict / n_records / summary: as lamd_gossip_store_audit, unchanged in meaning.  new_off / reason:
+ * cap entries each.  The output goes to `out` (host) and / or stays on the device at d_out; out_cap is the size of each one given, both
+ * may be NULL (the maps and the counters only).  A device buffer of len + 46 bytes always suffices.  Too few entries: LAMD_ERR_ARG with
+ * *n_records = the count needed.  out_cap too small: LAMD_ERR_ARG with repair->out_len = the size needed and everything else filled in;
+ * what d_out then holds is unspecified (nothing is written behind out_cap).
+ * The device work is queued behind the audit's on the same stream: keep flags (k_store_keep_chan: announcements, and their node ids into
+ * a table; k_store_keep_rest: everything else), the exclusive scan of the kept sizes (reduce, scan of the sums, apply: separate launches),
+ * the copy (k_store_pack: one aligned 32-bit word of the output per lane).  The host waits twice: for verdicts, reasons, offsets and the
+ * output's length, then -- with `out` -- for that many bytes of image.  A store holding only its version byte gives version + uuid record. */
+int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32, size_t cap,
+			     uint64_t *rec_off, int8_t *verdict, uint64_t *new_off, uint8_t *reason, size_t *n_records, uint8_t *out,
+			     void *d_out, size_t out_cap, lamd_store_summary *summary, lamd_store_repair_summary *repair);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

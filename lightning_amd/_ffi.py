@@ -34,6 +34,12 @@ class LamdStoreSummary(ctypes.Structure):
                 ("no_channel", ctypes.c_uint64), ("bad_signature", ctypes.c_uint64 * 4), ("signatures", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 5)]
 
 
+class LamdStoreRepairSummary(ctypes.Structure):
+    """lamd_store_repair_summary (include/lightning_amd.h): what lamd_gossip_store_repair reports about the store it wrote"""
+    _fields_ = [("kept", ctypes.c_uint64), ("dropped_deleted", ctypes.c_uint64), ("dropped_verdict", ctypes.c_uint64), ("dropped_dependency", ctypes.c_uint64),
+                ("dropped_bookkeeping", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
+
+
 # name -> (restype, argtypes); every symbol of include/lightning_amd.h and include/lightning_amd_debug.h
 SYMBOLS = {
     "lamd_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
@@ -73,6 +79,8 @@ SYMBOLS = {
     "lamd_sigcheck_gossip_spans_device": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_sz, c_u8p]),
     "lamd_gossip_store_frame": (ctypes.c_int, [c_u8p, c_sz, c_sz, c_u8p, ctypes.POINTER(c_sz), ctypes.POINTER(LamdStoreSummary)]),
     "lamd_gossip_store_audit": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.POINTER(c_sz), ctypes.POINTER(LamdStoreSummary)]),
+    "lamd_gossip_store_repair": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.POINTER(c_sz), c_u8p,
+                                                ctypes.c_void_p, c_sz, ctypes.POINTER(LamdStoreSummary), ctypes.POINTER(LamdStoreRepairSummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

@@ -21,6 +21,7 @@
 #include "fuzz.h"
 #include "host_ranges.h"
 #include "store_audit.h"
+#include "store_repair.h"
 
 using namespace lamd;
 
@@ -494,6 +495,109 @@ __global__ void __launch_bounds__(256) k_store_verdict(u32 n, const int8_t *__re
   if (i >= n) return;
   const u32 j = sel[i];
   verdict[i] = (int8_t)store_merge_one(pre[i], j != STORE_NONE, j != STORE_NONE ? sigv[j] : 0, aux[i]);
+}
+
+// ---- gossip_store repair (lamd_gossip_store_repair; per-record and per-word logic in store_repair.h), behind k_store_verdict on the same stream.
+// k_store_keep_chan: the live channel_announcements -- reason and size, and the two node ids of each kept one into the node table
+// (nkeys / nvals: 1 << nbits slots, preset to all-ones bytes).  k_store_keep_rest: every other record (it reads the announcements' reasons,
+// so it is a launch of its own); lane n writes the closing size 0, so that the scan ends with the sum.
+__global__ void __launch_bounds__(256) k_store_keep_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                         const int8_t *__restrict__ verdict, u64 *nkeys, u32 *nvals, u32 nbits, u8 *__restrict__ reason,
+                                                         u32 *__restrict__ size) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !store_is_live_cann(store, store_len, rec_off[i])) return;
+  u32 sz;
+  u64 idoff = 0;
+  const u32 r = store_keep_cann(store, store_len, rec_off, verdict, n, i, &sz, &idoff);
+  reason[i] = (u8)r;
+  size[i] = sz;
+  if (r == STORE_DROP_KEPT) {
+    store_node_insert(store, nkeys, nvals, nbits, idoff, i);
+    store_node_insert(store, nkeys, nvals, nbits, idoff + 33, i);
+  }
+}
+__global__ void __launch_bounds__(256) k_store_keep_rest(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                         const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
+                                                         u32 bits, const u64 *__restrict__ nkeys, const u32 *__restrict__ nvals, u32 nbits, u8 *reason,
+                                                         u32 *__restrict__ size) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  if (i == n) { size[n] = 0; return; }
+  if (store_is_live_cann(store, store_len, rec_off[i])) return;
+  u32 sz;
+  reason[i] = (u8)store_keep_other(store, store_len, rec_off, verdict, n, i, keys, vals, bits, nkeys, nvals, nbits, reason, &sz);
+  size[i] = sz;
+}
+// The exclusive scan of the sizes, 64-bit, in tiles of STORE_SCAN_TILE = one block: k_store_scan_reduce leaves one sum per tile, the sums are
+// scanned the same way (level by level until one tile holds them), k_store_scan_apply scans inside each tile and adds the tile's base.
+// Separate launches, no workgroup waits for another.  With new_off (the record level) it also writes the records' offsets in the output.
+template <class In>
+__global__ void __launch_bounds__(256) k_store_scan_reduce(u64 n, const In *__restrict__ in, u64 *__restrict__ sums) {
+  __shared__ u64 w[4];
+  const u32 t = threadIdx.x;
+  const u64 i = (u64)blockIdx.x * STORE_SCAN_TILE + t;
+  u64 v = i < n ? (u64)in[i] : 0;
+  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
+  if ((t & 63) == 0) w[t >> 6] = v;
+  __syncthreads();
+  if (t == 0) sums[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
+}
+template <class In>
+__global__ void __launch_bounds__(256) k_store_scan_apply(u64 n, const In *in, const u64 *__restrict__ base, u64 *out, u64 n_rec,
+                                                          const u8 *__restrict__ reason, u64 *__restrict__ new_off) {
+  __shared__ u64 s[STORE_SCAN_TILE];
+  const u32 t = threadIdx.x;
+  const u64 i = (u64)blockIdx.x * STORE_SCAN_TILE + t;
+  const u64 v = i < n ? (u64)in[i] : 0;
+  s[t] = v;
+  __syncthreads();
+  for (u32 d = 1; d < STORE_SCAN_TILE; d <<= 1) {
+    const u64 a = t >= d ? s[t - d] : 0;
+    __syncthreads();
+    s[t] += a;
+    __syncthreads();
+  }
+  if (i >= n) return;
+  const u64 x = s[t] - v + (base ? base[blockIdx.x] : 0);
+  out[i] = x;
+  if (new_off && i < n_rec) new_off[i] = reason[i] == STORE_DROP_KEPT ? STORE_REPAIR_HEAD + x : ~(u64)0;
+}
+// k_store_pack: one aligned 32-bit word of the OUTPUT per lane and step, 256 consecutive words per block and step: the stores of a wave
+// are 256 contiguous bytes whatever the records' lengths and alignments, and a lane's time does not depend on any record's length.  A
+// block owns STORE_PACK_WORDS consecutive words; lanes 0 and 1 find the records of its first and last payload byte in the whole scan, the
+// block stages that window of the scan and of the record offsets in LDS and every lane searches there (a window of more than
+// STORE_PACK_STAGE records -- a long run of dropped ones inside the block's bytes -- is searched in global memory instead).  The grid is
+// sized by the upper bound len + 46: blocks behind the output's end leave at once.
+constexpr u32 STORE_PACK_WORDS = 2048;
+__global__ void __launch_bounds__(256) k_store_pack(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                    const u64 *__restrict__ pos, store_head head, u8 *__restrict__ out, u64 out_cap) {
+  __shared__ u32 range[2];
+  __shared__ u32 rel[STORE_PACK_STAGE + 1];
+  __shared__ u64 roff[STORE_PACK_STAGE];
+  const u32 t = threadIdx.x, mis = (u32)((uintptr_t)out & 3);
+  const u64 total = STORE_REPAIR_HEAD + pos[n], lim = out_cap < total ? out_cap : total;
+  const u64 k0 = (u64)blockIdx.x * STORE_PACK_WORDS, k1 = k0 + STORE_PACK_WORDS;
+  if (4 * k0 >= lim + mis) return;
+  if (t < 2) {
+    const u64 bf = 4 * k0 > mis ? 4 * k0 - mis : 0, bl = 4 * k1 - mis < lim ? 4 * k1 - mis : lim;   // the block's bytes: [bf, bl)
+    u32 r = 0;
+    if (bl > STORE_REPAIR_HEAD)
+      r = store_pack_locate(store_pack_global{rec_off, pos}, 0, n - 1, t ? bl - STORE_REPAIR_HEAD - 1 : (bf > STORE_REPAIR_HEAD ? bf - STORE_REPAIR_HEAD : 0));
+    range[t] = r;
+  }
+  __syncthreads();
+  const u32 lo = range[0], hi = range[1];
+  if (hi - lo < STORE_PACK_STAGE) {
+    const u64 base = pos[lo];
+    for (u32 j = t; j <= hi - lo + 1; j += 256) rel[j] = (u32)(pos[lo + j] - base);
+    for (u32 j = t; j <= hi - lo; j += 256) roff[j] = rec_off[lo + j];
+    __syncthreads();
+    const store_pack_staged v{roff, rel, lo, base};
+    for (u64 k = k0 + t; k < k1; k += 256) store_pack_word(store, store_len, v, lo, hi, head, out, lim, mis, k);
+  } else {
+    const store_pack_global v{rec_off, pos};
+    for (u64 k = k0 + t; k < k1; k += 256) store_pack_word(store, store_len, v, lo, hi, head, out, lim, mis, k);
+  }
 }
 
 // (the synthetic-workload signer kernels live in lamd_testgen.hip -> liblightning_amd_testgen.so: test / bench infrastructure,
@@ -1608,6 +1712,8 @@ struct lamd_ctx {
   devbuf g_msgs, g_off, g_ids, g_rowbase, g_hash, g_sig, g_pub, g_malformed, g_ok, g_verdict;
   devbuf st_img, st_host, st_ids, st_tab, st_out;   // gossip_store audit: image, the host walk's arrays, signers, scid index, per-record bytes
   hipEvent_t ev_store[6] = {};                      // ... and its stage boundaries (created when a timed audit first runs)
+  devbuf st_rep, st_pack;                           // gossip_store repair: reasons, sizes, offsets, block sums, node table; the output image
+  hipEvent_t ev_rep[4] = {};                        // ... and its stage boundaries
   // timing
   bool timing = false;
   bool ev_recorded = false;
@@ -1989,9 +2095,12 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
   for (devbuf *b : {&ctx->small_done, &ctx->recs, &ctx->qwords, &ctx->keyok, &ctx->slots, &ctx->vbuf, &ctx->in_a, &ctx->in_b, &ctx->in_c, &ctx->out,
                     &ctx->g_msgs, &ctx->g_off, &ctx->g_ids, &ctx->g_rowbase, &ctx->g_hash, &ctx->g_sig, &ctx->g_pub,
-                    &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict, &ctx->st_img, &ctx->st_host, &ctx->st_ids, &ctx->st_tab, &ctx->st_out})
+                    &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict, &ctx->st_img, &ctx->st_host, &ctx->st_ids, &ctx->st_tab, &ctx->st_out, &ctx->st_rep,
+                    &ctx->st_pack})
     release(b);
   for (auto &e : ctx->ev_store)
+    if (e) (void)hipEventDestroy(e);
+  for (auto &e : ctx->ev_rep)
     if (e) (void)hipEventDestroy(e);
   for (auto &qs : ctx->qs) {
     for (auto &q : qs.q) {
@@ -3706,11 +3815,22 @@ extern "C" int lamd_gossip_store_frame(const uint8_t *store, size_t len, size_t 
   return summary->records > cap ? LAMD_ERR_ARG : LAMD_OK;
 }
 // Everything between the host walk and the final copy is queued on one lane's stream: image (unless resident) and the walk's arrays up,
-// four kernels and the signature batch, the verdict bytes down.
-extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off,
-                                       int8_t *verdict, size_t *n_records, lamd_store_summary *summary) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!store || !n_records || !summary || (cap && (!rec_off || !verdict))) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+// four kernels and the signature batch, the verdict bytes down.  store_job: what the queued stages leave on the device for the caller --
+// lamd_gossip_store_audit copies the verdicts down, lamd_gossip_store_repair queues its own stages behind them first.
+struct store_job {
+  lamd_ctx *L = nullptr;      // the lane; nullptr: nothing is queued (no record, or an error before the first copy)
+  size_t n = 0, n_cann = 0;   // records; live channel_announcements
+  const u8 *img = nullptr;    // the image on the device
+  const u64 *d_recoff = nullptr;
+  const u64 *d_keys = nullptr;
+  const u32 *d_vals = nullptr;
+  u32 bits = 0;               // the scid index
+  const int8_t *d_verdict = nullptr;
+  std::vector<u64> pack;      // the queued copy reads it: lives until the stream has been synchronised
+};
+#define STCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { L->err = std::string(#call) + ": " + hipGetErrorString(e_); return fail(LAMD_ERR_HIP); } } while (0)
+static int store_audit_queue(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off, size_t *n_records,
+                             lamd_store_summary *summary, store_job *job) {
   *n_records = 0;
   // the walk: record offsets, and the selection of the signature batch -- the live 256 / 257 / 258 records (4 rows / 1 / 1)
   std::vector<u64> start, mlen, rowbase;
@@ -3736,7 +3856,7 @@ extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size
   if (n > cap) { ctx->err = "gossip_store audit: rec_off / verdict too small"; return LAMD_ERR_ARG; }
   if (n >= (size_t)STORE_NONE || rows >= (u64)STORE_NONE) { ctx->err = "gossip_store audit: too many records"; return LAMD_ERR_ARG; }
   summary->signatures = rows;
-  if (n == 0) { store_count_verdicts(verdict, 0, summary); return LAMD_OK; }
+  if (n == 0) return LAMD_OK;
   rowbase.push_back(rows);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   lamd_ctx *L;
@@ -3746,7 +3866,8 @@ extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size
   while (((size_t)1 << bits) < 2 * n_cann) bits++;
   const size_t slots = ((size_t)1 << bits) + 1;
   // host arrays, one copy: rec_off u64[n] | start u64[nsel] | len u64[nsel] | rowbase u64[nsel + 1] | sel u32[n]
-  std::vector<u64> pack(n + 3 * nsel + 1 + (n + 1) / 2);
+  std::vector<u64> &pack = job->pack;
+  pack.assign(n + 3 * nsel + 1 + (n + 1) / 2, 0);
   for (size_t i = 0; i < n; i++) pack[i] = rec_off[i];
   if (nsel) {
     memcpy(&pack[n], start.data(), 8 * nsel);
@@ -3777,7 +3898,6 @@ extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size
   int8_t *d_pre = L->st_out.as<int8_t>(), *d_verdict = d_pre + n, *d_sigv = d_verdict + n;
   u8 *d_aux = (u8 *)(d_sigv + nsel);
   const u8 *img = (const u8 *)d_store;
-#define STCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { L->err = std::string(#call) + ": " + hipGetErrorString(e_); return fail(LAMD_ERR_HIP); } } while (0)
   if (!d_store) {
     STCHK(hipMemcpyAsync(L->st_img.p, store, len, hipMemcpyHostToDevice, st));
     img = L->st_img.as<const u8>();
@@ -3803,18 +3923,170 @@ extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size
   hipLaunchKernelGGL(k_store_verdict, grid, block, 0, st, (u32)n, (const int8_t *)d_pre, d_sel, (const int8_t *)d_sigv, (const u8 *)d_aux, d_verdict);
   STCHK(hipGetLastError());
   if (timed) STCHK(hipEventRecord(L->ev_store[5], st));
-  STCHK(hipMemcpyAsync(verdict, d_verdict, n, hipMemcpyDeviceToHost, st));
-  STCHK(hipStreamSynchronize(st));
-  if (timed)
-    for (int k = 0; k < 5; k++) {
-      float ms = 0;
-      STCHK(hipEventElapsedTime(&ms, L->ev_store[k], L->ev_store[k + 1]));
-      summary->stage_ms[k] = ms;
-    }
-#undef STCHK
-  store_count_verdicts(verdict, n, summary);
+  job->L = L;
+  job->n = n;
+  job->n_cann = n_cann;
+  job->img = img;
+  job->d_recoff = d_recoff;
+  job->d_keys = d_keys;
+  job->d_vals = d_vals;
+  job->bits = bits;
+  job->d_verdict = d_verdict;
   return LAMD_OK;
 }
+// behind the synchronisation that ends a timed audit: the stage times
+static int store_audit_times(lamd_ctx *ctx, lamd_ctx *L, lamd_store_summary *summary) {
+  for (int k = 0; k < 5; k++) {
+    float ms = 0;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, L->ev_store[k], L->ev_store[k + 1]));
+    summary->stage_ms[k] = ms;
+  }
+  return LAMD_OK;
+}
+extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off,
+                                       int8_t *verdict, size_t *n_records, lamd_store_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!store || !n_records || !summary || (cap && (!rec_off || !verdict))) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  store_job job;
+  int rc = store_audit_queue(ctx, store, len, d_store, cap, rec_off, n_records, summary, &job);
+  if (rc != LAMD_OK) return rc;
+  lamd_ctx *L = job.L;
+  if (!L) { store_count_verdicts(verdict, 0, summary); return LAMD_OK; }
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(L->stream);
+    if (L != ctx) ctx->err = L->err;
+    return code;
+  };
+  STCHK(hipMemcpyAsync(verdict, job.d_verdict, job.n, hipMemcpyDeviceToHost, L->stream));
+  STCHK(hipStreamSynchronize(L->stream));
+  if (ctx->timing && (rc = store_audit_times(ctx, L, summary)) != LAMD_OK) return rc;
+  store_count_verdicts(verdict, job.n, summary);
+  return LAMD_OK;
+}
+
+// ---- gossip_store repair: the audit's stages, then keep flags, scan and copy on the same stream.  ONE wait more than the audit: the
+// verdicts, reasons, offsets and the output's length come down first (the length decides how much of the image follows).
+static void store_count_reasons(const uint8_t *reason, size_t n, lamd_store_repair_summary *r) {
+  for (size_t i = 0; i < n; i++) {
+    switch (reason[i]) {
+      case STORE_DROP_KEPT: r->kept++; break;
+      case STORE_DROP_DELETED: r->dropped_deleted++; break;
+      case STORE_DROP_VERDICT: r->dropped_verdict++; break;
+      case STORE_DROP_DEPENDENCY: r->dropped_dependency++; break;
+      default: r->dropped_bookkeeping++;
+    }
+  }
+}
+extern "C" int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32, size_t cap,
+                                        uint64_t *rec_off, int8_t *verdict, uint64_t *new_off, uint8_t *reason, size_t *n_records, uint8_t *out,
+                                        void *d_out, size_t out_cap, lamd_store_summary *summary, lamd_store_repair_summary *repair) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!store || !uuid32 || !n_records || !summary || !repair || (cap && (!rec_off || !verdict || !new_off || !reason))) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *repair = lamd_store_repair_summary();
+  store_job job;
+  int rc = store_audit_queue(ctx, store, len, d_store, cap, rec_off, n_records, summary, &job);
+  if (rc != LAMD_OK) return rc;
+  const store_head head = store_make_head(store[0], uuid32);
+  const bool want_out = out || d_out;
+  lamd_ctx *L = job.L;
+  if (!L) {   // no record: the version byte and the uuid record
+    store_count_verdicts(verdict, 0, summary);
+    repair->out_len = STORE_REPAIR_HEAD;
+    if (want_out && out_cap < STORE_REPAIR_HEAD) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
+    if (out) memcpy(out, head.b, STORE_REPAIR_HEAD);
+    if (d_out) {
+      HIPCHK(ctx, hipSetDevice(ctx->device));
+      HIPCHK(ctx, hipMemcpy(d_out, head.b, STORE_REPAIR_HEAD, hipMemcpyHostToDevice));
+    }
+    return LAMD_OK;
+  }
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(L->stream);
+    if (L != ctx) ctx->err = L->err;
+    return code;
+  };
+  const size_t n = job.n;
+  // the scan's levels: cnt[0] = n + 1 sizes (the last one 0), cnt[k + 1] = the tiles of level k, until one tile holds a level
+  std::vector<size_t> cnt{n + 1};
+  while (cnt.back() > STORE_SCAN_TILE) cnt.push_back((cnt.back() + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE);
+  size_t n_sums = 0;
+  for (size_t k = 1; k < cnt.size(); k++) n_sums += cnt[k];
+  u32 nbits = 1;
+  while (((size_t)1 << nbits) < 4 * job.n_cann) nbits++;
+  const size_t nslots = (size_t)1 << nbits, upper = len + STORE_REPAIR_HEAD - 1;   // upper: no output is longer
+  // pos u64[n + 1] | new_off u64[n] | sums u64[n_sums] | nkeys u64[nslots] | nvals u32[nslots] | size u32[n + 1] | reason u8[n]
+  if ((rc = ensure(L, &L->st_rep, 8 * (2 * n + 1 + n_sums + nslots) + 4 * (nslots + n + 1) + n + 16)) != LAMD_OK) return fail(rc);
+  if (want_out && !d_out && (rc = ensure(L, &L->st_pack, upper + 16)) != LAMD_OK) return fail(rc);
+  const bool timed = ctx->timing;
+  if (timed)
+    for (auto &e : L->ev_rep)
+      if (!e) STCHK(hipEventCreate(&e));
+  hipStream_t st = L->stream;
+  u64 *d_pos = L->st_rep.as<u64>(), *d_newoff = d_pos + n + 1, *d_sums = d_newoff + n, *d_nkeys = d_sums + n_sums;
+  u32 *d_nvals = (u32 *)(d_nkeys + nslots), *d_size = d_nvals + nslots;
+  u8 *d_reason = (u8 *)(d_size + n + 1);
+  u8 *d_img_out = d_out ? (u8 *)d_out : L->st_pack.as<u8>();
+  const size_t dev_cap = d_out ? out_cap : upper;
+  STCHK(hipMemsetAsync(d_nkeys, 0xFF, nslots * 12, st));
+  if (timed) STCHK(hipEventRecord(L->ev_rep[0], st));
+  hipLaunchKernelGGL(k_store_keep_chan, dim3(blocks_for(n)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, d_nkeys, d_nvals, nbits,
+                     d_reason, d_size);
+  hipLaunchKernelGGL(k_store_keep_rest, dim3(blocks_for(n + 1)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals,
+                     job.bits, (const u64 *)d_nkeys, (const u32 *)d_nvals, nbits, d_reason, d_size);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(L->ev_rep[1], st));
+  {
+    std::vector<u64 *> lvl{d_pos};   // level k >= 1 lives in d_sums and is scanned in place
+    for (size_t k = 1, o = 0; k < cnt.size(); o += cnt[k], k++) lvl.push_back(d_sums + o);
+    const size_t top = cnt.size() - 1;
+    for (size_t k = 0; k < top; k++) {
+      if (k == 0) hipLaunchKernelGGL(k_store_scan_reduce<u32>, dim3((unsigned)cnt[1]), dim3(256), 0, st, (u64)cnt[0], (const u32 *)d_size, lvl[1]);
+      else hipLaunchKernelGGL(k_store_scan_reduce<u64>, dim3((unsigned)cnt[k + 1]), dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], lvl[k + 1]);
+    }
+    for (size_t k = top + 1; k-- > 0;) {
+      const u64 *base = k == top ? nullptr : lvl[k + 1];
+      const dim3 grid((unsigned)((cnt[k] + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE));
+      if (k == 0) hipLaunchKernelGGL(k_store_scan_apply<u32>, grid, dim3(256), 0, st, (u64)cnt[0], (const u32 *)d_size, base, d_pos, (u64)n, (const u8 *)d_reason, d_newoff);
+      else hipLaunchKernelGGL(k_store_scan_apply<u64>, grid, dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], base, lvl[k], (u64)0, (const u8 *)nullptr, (u64 *)nullptr);
+    }
+  }
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(L->ev_rep[2], st));
+  if (want_out && dev_cap) {
+    const size_t words = (3 + (upper < dev_cap ? upper : dev_cap)) / 4 + 1;
+    hipLaunchKernelGGL(k_store_pack, dim3((unsigned)((words + STORE_PACK_WORDS - 1) / STORE_PACK_WORDS)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff,
+                       (const u64 *)d_pos, head, d_img_out, (u64)dev_cap);
+    STCHK(hipGetLastError());
+  }
+  if (timed) STCHK(hipEventRecord(L->ev_rep[3], st));
+  u64 payload = 0;
+  STCHK(hipMemcpyAsync(verdict, job.d_verdict, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(reason, d_reason, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(new_off, d_newoff, 8 * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&payload, d_pos + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed) {
+    if ((rc = store_audit_times(ctx, L, summary)) != LAMD_OK) return rc;
+    for (int k = 0; k < 3; k++) {
+      float ms = 0;
+      STCHK(hipEventElapsedTime(&ms, L->ev_rep[k], L->ev_rep[k + 1]));
+      repair->stage_ms[k] = ms;
+    }
+  }
+  store_count_verdicts(verdict, n, summary);
+  store_count_reasons(reason, n, repair);
+  repair->out_len = STORE_REPAIR_HEAD + payload;
+  if (want_out && repair->out_len > out_cap) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
+  if (out) {
+    STCHK(hipMemcpyAsync(out, d_img_out, repair->out_len, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
+  }
+  return LAMD_OK;
+}
+#undef STCHK
 
 extern "C" int lamd_sigcheck_gossip_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *off,
                                           const uint8_t *node_ids33, int8_t *verdict) {

@@ -33,6 +33,12 @@ def _store_summary(s):
     return d
 
 
+def _repair_summary(r):
+    d = {k: int(getattr(r, k)) for k in ("kept", "dropped_deleted", "dropped_verdict", "dropped_dependency", "dropped_bookkeeping", "out_len")}
+    d["stage_ms"] = list(r.stage_ms)
+    return d
+
+
 def _store_blob(blob):
     a = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, dtype=np.uint8)
     return a, a.size, (a if a.size else np.zeros(1, dtype=np.uint8))
@@ -302,6 +308,38 @@ class Engine:
         self._chk(self._lib.lamd_gossip_store_audit(self._ctx, buf.ctypes.data, n_bytes, d_ptr, n, off.ctypes.data, verdict.ctypes.data, ctypes.byref(cnt),
                                                     ctypes.byref(s)))
         return off[:cnt.value], verdict[:cnt.value], _store_summary(s)
+
+    def gossip_store_repair(self, blob, uuid, d_store=None, d_out=None, host_out=True):
+        """lamd_gossip_store_repair over a gossip_store image (bytes or numpy uint8): the audit, then the store that holds the records which passed and
+        whose dependencies passed, behind a fresh uuid record (uuid: 32 bytes).  d_store: the image resident in a torch uint8 CUDA tensor.
+        d_out: a torch uint8 CUDA tensor the output is left in (len(blob) + 46 bytes always suffice); host_out=False: no copy to the host.
+        -> (out bytes or None, rec_off uint64 [records], verdict int8 [records], new_off uint64 [records] (2**64 - 1: dropped), reason uint8 [records],
+            audit summary dict, repair summary dict)"""
+        _, n_bytes, buf = _store_blob(blob)
+        uuid = np.frombuffer(bytes(uuid), dtype=np.uint8)
+        if uuid.size != 32:
+            raise ValueError("the uuid has 32 bytes")
+        cnt, s, r = ctypes.c_size_t(0), _ffi.LamdStoreSummary(), _ffi.LamdStoreRepairSummary()
+        self._lib.lamd_gossip_store_frame(buf.ctypes.data, n_bytes, 0, None, ctypes.byref(cnt), ctypes.byref(s))   # the count; the repair reports every error itself
+        n = cnt.value
+        off, verdict = np.zeros(max(1, n), dtype=np.uint64), np.zeros(max(1, n), dtype=np.int8)
+        new_off, reason = np.zeros(max(1, n), dtype=np.uint64), np.zeros(max(1, n), dtype=np.uint8)
+        d_ptr = d_out_ptr = None
+        if d_store is not None:
+            if d_store.numel() != n_bytes:
+                raise ValueError("the resident image and the host image differ in size")
+            d_ptr = d_store.data_ptr()
+        out_cap = n_bytes + 46
+        if d_out is not None:
+            d_out_ptr, out_cap = d_out.data_ptr(), d_out.numel()
+        if d_store is not None or d_out is not None:
+            self._after_torch()
+        out = np.zeros(out_cap, dtype=np.uint8) if host_out else None
+        self._chk(self._lib.lamd_gossip_store_repair(self._ctx, buf.ctypes.data, n_bytes, d_ptr, uuid.ctypes.data, n, off.ctypes.data, verdict.ctypes.data,
+                                                     new_off.ctypes.data, reason.ctypes.data, ctypes.byref(cnt), out.ctypes.data if host_out else None, d_out_ptr,
+                                                     out_cap, ctypes.byref(s), ctypes.byref(r)))
+        k = cnt.value
+        return (out[:r.out_len].tobytes() if host_out else None, off[:k], verdict[:k], new_off[:k], reason[:k], _store_summary(s), _repair_summary(r))
 
     # ---- single-item veneers (reference semantics)
     def check_signed_hash(self, hash32, sig64, pubkey):

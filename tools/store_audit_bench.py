@@ -5,6 +5,9 @@ against lamd_sigcheck_gossip_spans_device over the same messages with host-suppl
 chosen per process: run once with --ways 4 and once with --ways 8.
 
     python tools/store_audit_bench.py --ways 8 [--cann 150000 --cupd 450000 --runs 10]
+
+--repair adds lamd_gossip_store_repair over the same image (resident in, output left resident): the keep, scan and pack stages from HIP
+events, a plain device-to-device copy of out_len bytes timed the same way (the yardstick of k_store_pack), and the whole call next to the audit's.
 """
 import argparse
 import json
@@ -17,6 +20,7 @@ ap.add_argument("--ways", type=int, default=4, choices=(4, 8))
 ap.add_argument("--cann", type=int, default=150_000)
 ap.add_argument("--cupd", type=int, default=450_000)
 ap.add_argument("--runs", type=int, default=10)
+ap.add_argument("--repair", action="store_true")
 args = ap.parse_args()
 os.environ["LAMD_STORE_CRC_WAYS"] = str(args.ways)     # read once, at the first audit of the process
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
@@ -105,7 +109,47 @@ with Engine(0) as eng:
     res_untimed = [audit(True)[0] for _ in range(args.runs)]
     host = [audit(False)[0] for _ in range(3)]
     names = ("crc", "index", "signers", "signatures", "verdict")
-    print(json.dumps(dict(
+    repair = {}
+    if args.repair:
+        uuid = bytes(range(32))
+        d_out = torch.zeros(image.size + 46, dtype=torch.uint8, device="cuda")
+
+        def rep(host_out):
+            t0 = time.perf_counter()
+            out = eng.gossip_store_repair(image, uuid, d_store=d_image, d_out=d_out, host_out=host_out)
+            return (time.perf_counter() - t0) * 1e3, out
+
+        _, (_, _, rv, new_off, reason, _, r) = rep(False)
+        assert np.array_equal(rv, verdict), "repair verdicts differ from the audit's"
+        out_len = r["out_len"]
+        # closure: the output audits clean and holds the kept records behind its uuid record
+        fixed = d_out[:out_len].cpu().numpy()
+        _, _, s2 = eng.gossip_store_audit(fixed, d_store=d_out[:out_len])
+        assert s2["clean"] == 1 and s2["records"] == r["kept"] + 1, (s2, r)
+        eng.set_timing(True)
+        timed, rstages = [], []
+        for _ in range(args.runs):
+            ms, out = rep(False)
+            timed.append(ms)
+            rstages.append(out[6]["stage_ms"])
+        eng.set_timing(False)
+        untimed = [rep(False)[0] for _ in range(args.runs)]
+        with_host = [rep(True)[0] for _ in range(3)]
+        d_copy, copies = torch.empty(out_len, dtype=torch.uint8, device="cuda"), []
+        for _ in range(args.runs + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            d_copy.copy_(d_out[:out_len])
+            e1.record()
+            e1.synchronize()
+            copies.append(e0.elapsed_time(e1))
+        pack_med, copy_med = spread([st[2] for st in rstages])["median"], spread(copies[1:])["median"]
+        repair = dict(repair=dict(
+            out_len=out_len, kept=r["kept"], dropped=[r[k] for k in ("dropped_deleted", "dropped_verdict", "dropped_dependency", "dropped_bookkeeping")],
+            repair_resident_call_ms=spread(untimed), repair_resident_call_timed_ms=spread(timed), repair_resident_host_out_call_ms=spread(with_host),
+            stage_ms={n: spread([st[k] for st in rstages]) for k, n in enumerate(("keep", "scan", "pack"))},
+            d2d_copy_ms=spread(copies[1:]), pack_over_copy=round(pack_med / copy_med, 2), new_stages_ms=spread([sum(st) for st in rstages])))
+    print(json.dumps(dict(repair,
         crc_ways=args.ways, records=s["records"], signatures=s["signatures"], image_bytes=int(image.size), runs=args.runs,
         spans_call_ms=spread(base), audit_resident_call_ms=spread(res_untimed), audit_resident_call_timed_ms=spread(res), audit_host_image_call_ms=spread(host),
         stage_ms={n: spread([st[k] for st in stages]) for k, n in enumerate(names)},
