@@ -96,6 +96,51 @@ LAMD_HD gej gej_add_ge_fast(const gej &a, const ge &b) {
   return r;
 }
 
+// A comb column adds TWO affine points of the same curve to the accumulator.  Their sum is formed first -- affine + affine needs no inversion
+// when the result may be Jacobian: H = x2 - x1, R = y2 - y1, X = R^2 - H^3 - 2*x1*H^2, Y = R*(x1*H^2 - X) - y1*H^3, Z = H (2M + 2S + one
+// two-product reduction) -- and its Z^2 = H^2, Z^3 = H^3 are by-products, so the Jacobian + Jacobian addition that follows (gej_add_pair_fast)
+// does not compute them: pair sum + that addition is 15M + 5S where two mixed additions are 16M + 6S.
+// Bare like gej_add_ge_fast: a = +-b gives H = 0, hence Z = ZZ = ZZZ = 0.  a.y, b.y may have magnitude 2 (ge_neg_if_lazy).
+struct gejzz {
+  fe x, y, z, zz, zzz;  // all magnitude 1; zz = z^2, zzz = z^3
+};
+LAMD_HD gejzz ge_add_ge_fast(const ge &a, const ge &b) {
+  LAMD_ASSERT(FE_MAG(a.y) <= 2 && FE_MAG(b.y) <= 2);
+  gejzz r;
+  const fe ny = fe_neg(a.y, 2);                                      // -y1         (3)
+  r.z = fe_norm_weak(fe_add(b.x, fe_neg(a.x, 1)));                   // H = x2 - x1 (3) -> (1)
+  const fe rr = fe_norm_weak(fe_add(b.y, ny));                       // R = y2 - y1 (5) -> (1)
+  r.zz = fe_sqr(r.z);
+  r.zzz = fe_mul(r.z, r.zz);
+  const fe v = fe_mul(a.x, r.zz);
+  r.x = fe_sqr_add(rr, fe_neg(fe_add(r.zzz, fe_mul_int(v, 2)), 3));  // R^2 - H^3 - 2V
+  const fe t = fe_add(v, fe_neg(r.x, 1));  // (3)
+  r.y = fe_mul2(rr, t, ny, r.zzz);                                   // R*(V - X3) + (-y1)*H^3: 1*3 + 3*1
+  return r;
+}
+// r = a + b for Jacobian a and a pair sum b with its Z^2, Z^3; 11M + 3S.  The order lets b.zz / b.zzz die after U1 / S1 and a.x / a.y with them.
+// Z3 = Z1*Z2*H as two multiplications (198 multiply-adds): ((Z1 + Z2)^2 - ZZ1 - ZZ2)*H is 171 but wants Z1 + Z2 (magnitude 3) weakly
+// normalised first and every other product of the formula in its doubled form -- no fewer instructions.
+// Bare: H = 0 (a = +-b) or a zero Z of either operand makes Z3 zero, which stays zero as described above gej_add_ge_fast.
+LAMD_HD gej gej_add_pair_fast(const gej &a, const gejzz &b) {
+  gej r;
+  const fe u1 = fe_mul(a.x, b.zz);
+  const fe s1 = fe_mul(a.y, b.zzz);
+  const fe zz = fe_sqr(a.z);
+  const fe h = fe_mul_add(b.x, zz, fe_neg(u1, 1));                   // U2 - U1
+  const fe rr = fe_mul_add(b.y, fe_mul(a.z, zz), fe_neg(s1, 1));     // S2 - S1
+  const fe zt = fe_mul(a.z, b.z);                                    // z magnitude <= 2
+  const fe hh = fe_sqr(h);
+  const fe hhh = fe_mul(h, hh);
+  const fe v = fe_mul(u1, hh);
+  r.x = fe_sqr_add(rr, fe_neg(fe_add(hhh, fe_mul_int(v, 2)), 3));   // R^2 - H^3 - 2V
+  const fe t = fe_add(v, fe_neg(r.x, 1));  // (3)
+  r.y = fe_mul2(rr, t, s1, fe_neg(hhh, 1));                          // R*(V - X3) - S1*H^3
+  r.z = fe_mul(zt, h);
+  r.inf = false;
+  return r;
+}
+
 // XYZZ coordinates (x = X/ZZ, y = Y/ZZZ with ZZ^3 = ZZZ^2) for a RUN of bare mixed additions with no doubling in between -- the eleven windows
 // of u1*G at the end of a verification.  The Jacobian addition above recomputes Z^2 and Z^3 from Z in every step; here they are carried:
 // ZZ3 = ZZ1*H^2, ZZZ3 = ZZZ1*H^3 (two multiplications where the Jacobian form has Z^2, Z*Z^2 and Z1*H: a squaring less per addition), and the

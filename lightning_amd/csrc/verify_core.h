@@ -853,10 +853,12 @@ LAMD_HD comb_pair<T> comb_from_rec_odd(const prep_rec &rec) {
   return r;
 }
 
-// The hot form of the table-driven ecmult: both halves odd (no repair additions), the first column initialises the
-// accumulator (no infinity handling), every addition is the bare formula (gej_add_ge_fast) and the G windows skip a zero
-// digit by branching.  Degenerate events (an addition meeting +-its operand: adversarial scalars only, or the result being
-// infinity) leave Z = 0, which the caller tests ONCE: *suspect = true means "verdict unknown, run ecmult_lane_keyed".
+// The hot form of the table-driven ecmult: both halves odd (no repair additions), a column's two table points -- affine points of
+// the same curve -- are summed first and added to the accumulator as ONE pair (group.h ge_add_ge_fast + gej_add_pair_fast: 513 + 1 287
+// multiply-adds where two mixed additions are 1 980), the first column's pair is the accumulator (no infinity handling), every
+// formula is bare and the G windows skip a zero digit by branching.  Degenerate events (the column's points equal or opposite, an
+// addition meeting +-its operand: adversarial scalars only, or the result being infinity) leave Z = 0, which the caller tests ONCE:
+// *suspect = true means "verdict unknown, run ecmult_lane_keyed".
 template <int T>
 LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u32 *gtable, bool *suspect) {
   constexpr int D = kc_spacing(T), NE = kc_ne(T);
@@ -864,8 +866,10 @@ LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u
   gej acc = gej_infinity();
 #pragma unroll 1
   for (int j = D - 1; j >= 0; j--) {
+    // the doubling first: the pair's field elements are then not live across it
     if (j != D - 1) acc = gej_double(acc);
-#pragma unroll 1
+    ge pt[2];
+#pragma unroll
     for (int half = 0; half < 2; half++) {
       u32 m = 0;
 #pragma unroll
@@ -873,18 +877,18 @@ LAMD_HD gexz ecmult_lane_keyed_fast(const prep_rec &rec, const u32 *tab, const u
       const bool top = (m >> (T - 1)) & 1u;
       const u32 idx = (top ? m : ~m) & (u32)(NE - 1);
       const u32 *e = tab + idx * SLOT_ENTRY_WORDS;
-      ge pt;
-      pt.x = slot_load_fe(e + (half ? ENT_BX : ENT_X));
-      pt.y = slot_load_fe(e + ENT_Y);
-      pt = ge_neg_if_lazy(pt, top == (half ? cp.n2 : cp.n1));
-      if (j == D - 1 && half == 0) {  // uniform across the wave: the first point is the accumulator
-        acc.x = pt.x;
-        acc.y = fe_norm_weak(pt.y);
-        acc.z = fe_set_int(1);
-        acc.inf = false;
-      } else {
-        acc = gej_add_ge_fast(acc, pt);
-      }
+      pt[half].x = slot_load_fe(e + (half ? ENT_BX : ENT_X));
+      pt[half].y = slot_load_fe(e + ENT_Y);
+      pt[half] = ge_neg_if_lazy(pt[half], top == (half ? cp.n2 : cp.n1));
+    }
+    const gejzz pair = ge_add_ge_fast(pt[0], pt[1]);
+    if (j == D - 1) {  // uniform across the wave: the first pair is the accumulator
+      acc.x = pair.x;
+      acc.y = pair.y;
+      acc.z = pair.z;
+      acc.inf = false;
+    } else {
+      acc = gej_add_pair_fast(acc, pair);
     }
   }
   acc.z = fe_mul(acc.z, slot_load_fe(tab + kc_words(T)));
