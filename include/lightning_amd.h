@@ -71,7 +71,13 @@ const char *lamd_version(void);
  * lamd_verify_ecdsa_batch: n independent check_signed_hash() calls (bitcoin/signature.c:174-192,
  * decl bitcoin/signature.h:85-87).  publen is 33 or 65 for every key of the batch; key i is at
  * pub + i*pubstride.  With publen 33 this is check_signed_hash_nodeid() (common/node_id.c:72-80).
- * 65-byte keys may be 0x04 or hybrid 0x06/0x07, as secp256k1_ec_pubkey_parse accepts them. */
+ * 65-byte keys may be 0x04 or hybrid 0x06/0x07, as secp256k1_ec_pubkey_parse accepts them.
+ *
+ * Key columns (every pubstride / keystride of this header, host or device memory): only the publen bytes of each key are read, so the
+ * buffer need hold (n-1)*pubstride + publen bytes -- the keys may be the last field of an array of structs; pubstride < publen is
+ * LAMD_ERR_ARG.  Alignment: the byte columns (hashes, messages, signatures, keys, recids, sighash types, preimage / message / TLV blobs,
+ * node ids, verdicts and key outputs) may start at ANY address, host or device; arrays of wider elements need their natural alignment --
+ * the uint64 offset, start, length, rowbase and amount arrays 8 bytes, the uint32 arrays 4. */
 int lamd_verify_ecdsa_batch(lamd_ctx *ctx, size_t n, const uint8_t *hash32, const uint8_t *sig64,
 			    const uint8_t *pub, size_t publen, size_t pubstride, uint8_t *ok);
 

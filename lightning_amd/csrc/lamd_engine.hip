@@ -20,6 +20,7 @@
 #include "verify_core.h"
 #include "fuzz.h"
 #include "host_ranges.h"
+#include "key_column.h"
 #include "store_audit.h"
 #include "store_repair.h"
 
@@ -3138,15 +3139,17 @@ static int run_host(lamd_ctx *ctx, int mode, size_t n, const u8 *a, const u8 *si
     if (rc != 1) return rc;
     ctx->force_learn = true;  // a key that missed before is back: this call builds and publishes the missing tables (general path below)
   }
+  size_t keybytes;  // of the caller's key column: it ends with its last key, not with that key's stride (key_column.h)
+  if (!lamd::key_column_bytes(n, (size_t)keylen, keystride, &keybytes)) { ctx->err = "bad argument"; ctx->force_learn = false; return LAMD_ERR_ARG; }
   if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_c, n * keystride)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->in_c, keybytes)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->out, n)) != LAMD_OK) return rc;
   // the keys first: key de-duplication and table building only need them.  All three copies stay on ONE stream: the caller's
   // buffers are pageable, so the runtime stages them itself (the call blocks while it does); issuing the hash / signature copies on
   // the prep stream instead gained nothing and a 1 M-row batch came back with 5 % wrong verdicts (pageable copies in flight on two
   // streams; not root-caused) -- the pinned staging sets of the streaming queue (lamd_flush) do split their transfers.
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, key, n * keystride, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, key, keybytes, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ctx->in_a.p, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ctx->in_b.p, sig, n * 64, hipMemcpyHostToDevice, ctx->stream));
   rc = run_device(ctx, mode, n, ctx->in_a.as<const u8>(), ctx->in_b.as<const u8>(), ctx->in_c.as<const u8>(), keylen, keystride,
@@ -3236,12 +3239,14 @@ extern "C" int lamd_pubkey_parse_batch(lamd_ctx *ctx, size_t n, const uint8_t *p
     ctx->err = "bad argument";
     return LAMD_ERR_ARG;
   }
+  size_t keybytes;
+  if (!lamd::key_column_bytes(n, publen, pubstride, &keybytes)) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc;
-  if ((rc = ensure(ctx, &ctx->in_c, n * pubstride)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->in_c, keybytes)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->qwords, n * 64)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->keyok, n)) != LAMD_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, n * pubstride, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, keybytes, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_keys, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, ctx->in_c.as<const u8>(), (int)publen, pubstride,
                      (const u32 *)nullptr, ctx->qwords.as<u32>(), ctx->keyok.as<u8>(), (const u32 *)nullptr);
   HIPCHK(ctx, hipGetLastError());
@@ -3270,6 +3275,8 @@ extern "C" int lamd_check_tx_sig_batch(lamd_ctx *ctx, size_t n, const uint8_t *p
     ctx->err = "bad argument";
     return LAMD_ERR_ARG;
   }
+  size_t keybytes;
+  if (!lamd::key_column_bytes(n, publen, pubstride, &keybytes)) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc;
   // a few rows (an unmodified channeld checks ONE signature per check_tx_sig() call, channeld.c:2171,2224): gate + double SHA-256 on the
@@ -3296,7 +3303,7 @@ extern "C" int lamd_check_tx_sig_batch(lamd_ctx *ctx, size_t n, const uint8_t *p
   if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_c, n * pubstride)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->in_c, keybytes)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->out, n)) != LAMD_OK) return rc;
   u8 *d_types = ctx->g_ids.as<u8>(), *d_wit = d_types + n;
   HIPCHK(ctx, hipMemcpyAsync(ctx->g_msgs.p, preimages + off[0], total, hipMemcpyHostToDevice, ctx->stream));
@@ -3304,7 +3311,7 @@ extern "C" int lamd_check_tx_sig_batch(lamd_ctx *ctx, size_t n, const uint8_t *p
   HIPCHK(ctx, hipMemcpyAsync(d_types, sighash_type, n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(d_wit, has_witness, n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ctx->in_b.p, sig64, n * 64, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, n * pubstride, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, keybytes, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_txsig_hash, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(),
                      (const u8 *)d_types, (const u8 *)d_wit, ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>());
   HIPCHK(ctx, hipGetLastError());
@@ -3368,17 +3375,19 @@ static int txsig_tx_general(lamd_ctx *ctx, size_t n, const uint32_t *version, co
                             const uint8_t *scripts, const uint64_t *script_off, const uint8_t *sighash_type, const uint8_t *has_witness, const uint8_t *sig64,
                             const uint8_t *pub, size_t publen, size_t pubstride, uint8_t *ok) {
   int rc;
+  size_t keybytes;
+  if (!lamd::key_column_bytes(n, publen, pubstride, &keybytes)) { ctx->err = "bad argument"; ctx->force_learn = false; return LAMD_ERR_ARG; }
   txsig_blob B;
   txsig_pack(B, n, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type, has_witness);
   if ((rc = ensure(ctx, &ctx->g_msgs, B.total)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_c, n * pubstride)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->in_c, keybytes)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->out, n)) != LAMD_OK) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->g_msgs.p, B.st.data(), B.total, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ctx->in_b.p, sig64, n * 64, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, n * pubstride, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, keybytes, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = txsig_hash_launch(ctx, n, B, ctx->g_msgs.as<const u8>(), ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>())) != LAMD_OK) return rc;
   rc = run_device(ctx, MODE_ECDSA, n, ctx->in_a.as<const u8>(), ctx->in_b.as<const u8>(), ctx->in_c.as<const u8>(), (int)publen, pubstride,
                   ctx->out.as<u8>());

@@ -23,6 +23,18 @@ def _u8(a, shape_tail):
     return a
 
 
+def _key_column(pub, layout):
+    """the key column of a call -> (array to keep alive, key length, stride).  layout None: pub is [n, keylen], packed (stride = keylen).
+    layout (keylen, stride): pub is a flat uint8 buffer with key i at i * stride, handed to the library where it lies -- it need hold no
+    more than (n - 1) * stride + keylen bytes"""
+    if layout is None:
+        pub = np.ascontiguousarray(pub, dtype=np.uint8)
+        return pub, pub.shape[1], pub.shape[1]
+    if pub.dtype != np.uint8 or pub.ndim != 1 or not pub.flags.c_contiguous:
+        raise ValueError("a strided key column is a flat C-contiguous uint8 buffer")
+    return pub, int(layout[0]), int(layout[1])
+
+
 STORE_END_REASONS = ("eof", "partial_header", "incomplete", "truncated", "short", "store_ended", "no_amount")   # LAMD_STORE_END_*
 
 
@@ -121,8 +133,9 @@ class Engine:
                                                       ok.ctypes.data))
         return ok.astype(bool)
 
-    def check_tx_sig_batch(self, preimages, sighash_types, has_witness, sig64, pub):
-        """preimages: list of bytes (BIP143 preimages); returns bool verdicts (gate + SHA256d + verify, all on the device)"""
+    def check_tx_sig_batch(self, preimages, sighash_types, has_witness, sig64, pub, key_layout=None):
+        """preimages: list of bytes (BIP143 preimages); returns bool verdicts (gate + SHA256d + verify, all on the device).
+        key_layout (publen, pubstride): pub is a flat strided key column (_key_column)"""
         n = len(preimages)
         off = np.zeros(n + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(p) for p in preimages], dtype=np.uint64)
@@ -130,15 +143,16 @@ class Engine:
         types = np.ascontiguousarray(sighash_types, dtype=np.uint8)
         wit = np.ascontiguousarray(has_witness, dtype=np.uint8)
         sig64 = _u8(sig64, 64)
-        pub = np.ascontiguousarray(pub, dtype=np.uint8)
+        pub, publen, pubstride = _key_column(pub, key_layout)
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_check_tx_sig_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, types.ctypes.data, wit.ctypes.data,
-                                                    sig64.ctypes.data, pub.ctypes.data, pub.shape[1], pub.shape[1], ok.ctypes.data))
+                                                    sig64.ctypes.data, pub.ctypes.data, publen, pubstride, ok.ctypes.data))
         return ok.astype(bool)
 
-    def check_tx_sig_tx_batch(self, txs, sig64, pub):
+    def check_tx_sig_tx_batch(self, txs, sig64, pub, key_layout=None):
         """txs: list of dicts {version, locktime, inputs: [(txid32, vout, sequence)], outputs: [(amount, spk)], input_num, amount, script,
-        sighash_type, has_witness}; the BIP143 sighash is computed on the device (lamd_check_tx_sig_tx_batch).  Returns bool verdicts."""
+        sighash_type, has_witness}; the BIP143 sighash is computed on the device (lamd_check_tx_sig_tx_batch).  Returns bool verdicts.
+        key_layout (publen, pubstride): pub is a flat strided key column (_key_column)"""
         n = len(txs)
         u32 = lambda k: np.array([t[k] for t in txs], dtype=np.uint32)
         inputs = b"".join(b"".join(bytes(i[0]) + int(i[1]).to_bytes(4, "little") + int(i[2]).to_bytes(4, "little") for i in t["inputs"]) for t in txs)
@@ -156,12 +170,12 @@ class Engine:
         types = np.array([t["sighash_type"] for t in txs], dtype=np.uint8)
         wit = np.array([1 if t["has_witness"] else 0 for t in txs], dtype=np.uint8)
         sig64 = _u8(sig64, 64)
-        pub = np.ascontiguousarray(pub, dtype=np.uint8)
+        pub, publen, pubstride = _key_column(pub, key_layout)
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_check_tx_sig_tx_batch(self._ctx, n, ver.ctypes.data, lock.ctypes.data, ib.ctypes.data, in_off.ctypes.data, inum.ctypes.data,
                                                        amt.ctypes.data, ob.ctypes.data, out_off.ctypes.data, nout.ctypes.data, sb.ctypes.data,
                                                        sc_off.ctypes.data, types.ctypes.data, wit.ctypes.data, sig64.ctypes.data, pub.ctypes.data,
-                                                       pub.shape[1], pub.shape[1], ok.ctypes.data))
+                                                       publen, pubstride, ok.ctypes.data))
         return ok.astype(bool)
 
     def commitment_call(self, commit_tx, remote_funding33, commit_sig64, commit_sighash_type, htlc_txs, remote_htlckey33, htlc_sigs64, htlc_sighash_types):
@@ -208,13 +222,15 @@ class Engine:
         off = np.concatenate([[0], np.cumsum([len(x) for x in streams])]).astype(np.uint64)
         return np.frombuffer(b"".join(bytes(x) for x in streams) + b"\x00", dtype=np.uint8), off
 
-    def bolt12_check_signature_batch(self, streams, messagename, fieldname, key33, sig64):
-        """streams: list of serialised TLV streams; key33 uint8 [n,33]; sig64 uint8 [n,64] -> bool verdicts (lamd_bolt12_check_signature_batch)"""
+    def bolt12_check_signature_batch(self, streams, messagename, fieldname, key33, sig64, keystride=None):
+        """streams: list of serialised TLV streams; key33 uint8 [n,33]; sig64 uint8 [n,64] -> bool verdicts (lamd_bolt12_check_signature_batch).
+        keystride: key33 is a flat strided key column (_key_column)"""
         blob, off = self._streams(streams)
-        key33, sig64 = _u8(key33, 33), _u8(sig64, 64)
+        sig64 = _u8(sig64, 64)
+        key33, _, stride = _key_column(_u8(key33, 33) if keystride is None else key33, None if keystride is None else (33, keystride))
         ok = np.zeros(len(streams), dtype=np.uint8)
         self._chk(self._lib.lamd_bolt12_check_signature_batch(self._ctx, len(streams), blob.ctypes.data, off.ctypes.data, messagename, fieldname,
-                                                              key33.ctypes.data, 33, sig64.ctypes.data, ok.ctypes.data))
+                                                              key33.ctypes.data, stride, sig64.ctypes.data, ok.ctypes.data))
         return ok.astype(bool)
 
     def bolt12_merkle_batch(self, streams, messagename, fieldname):

@@ -71,6 +71,26 @@ class Net:
         return b"\x01\x01" + self.sign(self.node_sk[n] if sk is None else sk, body) + body
 
 
+def padding_edge_messages(net, n_cupd=12):
+    """Valid messages whose SIGNED TAILS (what sigcheck double-SHA-256s: everything behind the signatures) take every length mod 64, so that the
+    0x80 byte, the length words and the extra block of the padding fall everywhere: node_announcements with an address tail of 0..130 bytes
+    (tails of 76..206 bytes), channel_announcements with 0..66 feature bytes (174..240), a few channel_updates (72 bytes, and longer with extra bytes).
+    Laid back to back their starts take every residue mod 4.  -> [(msg, signer node id for a channel_update or None, length of the signed tail)]"""
+    r = net.rnd
+    out = []
+    for a in range(131):
+        m = net.nann(a % len(net.node_id), NOW - 5000 + a, addrs=bytes(r.randrange(256) for _ in range(a)))
+        out.append((m, None, len(m) - 66))
+    for f in range(67):
+        m = net.cann(f % len(net.chans), features=bytes(r.randrange(256) for _ in range(f)))
+        out.append((m, None, len(m) - 258))
+    for u in range(n_cupd):
+        c, d = u % len(net.chans), u & 1
+        m = net.cupd(c, d, NOW - 4000 + u, extra=bytes(r.randrange(256) for _ in range((0, 0, 47, 48, 55, 56)[u % 6])))
+        out.append((m, net.node_id[net.chans[c]["n"][d]], len(m) - 66))
+    return out
+
+
 def damage(rnd, m, kind):
     b = bytearray(m)
     if kind == "sig":            # a signature bit: "Bad ..." (or another verdict index)
