@@ -382,6 +382,67 @@ int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, size_t len, co
 			     uint64_t *rec_off, int8_t *verdict, uint64_t *new_off, uint8_t *reason, size_t *n_records, uint8_t *out,
 			     void *d_out, size_t out_cap, lamd_store_summary *summary, lamd_store_repair_summary *repair);
 
+/* ---- latest-wins repair of a gossip_store FILE: the repair above, and of the records that pass it only the one gossipd would hold now.
+ * The audit and the repair above answer "is every record intact, validly signed, and are its dependencies there?" and read no timestamp.
+ * Nor does the reference's load: update_channel() and node_announcement() (common/gossmap.c:585-610, :650-668) take whichever live record
+ * comes LAST in file order.  Timestamps are compared on the receive path alone -- `prev_timestamp >= timestamp` means ignore
+ * (gossipd/gossmap_manage.c:934-945, :1134-1143), timestamp_reasonable() (:997-1008) -- and gossipd flags what it supersedes DELETED
+ * (:964-966), so a store it wrote itself never shows the difference.  A copied, concatenated or edited store does: a validly signed old
+ * channel_update placed behind the current one is what gossmap then routes on; a header timestamp (the one gossipd's filters read,
+ * gossip_store_get_timestamp) may differ from the signed one under a recomputed CRC; a channel silent for more than two weeks stays until
+ * prune_network() (:409-471) first runs.
+ *
+ * Signed timestamp ts(i): channel_update -- the be32 at message offset 106; node_announcement -- the be32 at 68 + flen.
+ * ELIGIBLE: a live 257 / 258 with verdict OK whose header timestamp equals ts(i), and, with a clock (policy->now != 0), with
+ *           ts(i) <= now + future_slack (64-bit).
+ * WINNER of a set of records: the highest ts; among equal ts the LOWEST record index -- what `prev_timestamp >= timestamp: ignore` leaves
+ *           of records that arrive in file order.
+ * "Indexed announcement" as in the audit: the lowest-index live 256 of that scid, whatever its verdict.  In this order:
+ *   1  provisional announcements: as the repair decides (verdict OK, the amount record behind it OK)
+ *   2  per provisionally kept announcement a:  latest[a][d] = the winner among the eligible updates i > a whose indexed announcement is
+ *      a and whose channel_flags & 1 is d;  dying[a] = a live, OK, 14-byte 4106 record i > a names its scid
+ *   3  final announcements: a is STALE iff now != 0 and prune_interval != 0 and !dying[a] and, for some d, latest[a][d] exists with
+ *      ts + prune_interval < now (64-bit).  A direction without any update counts as fresh (get_timestamp() gives UINT32_MAX,
+ *      :383-396); ts == now - prune_interval keeps the channel (:440).  The node table holds the node ids of the FINALLY kept
+ *      announcements, lowest record index per node
+ *   4  nlatest[node] = the winner among the eligible 257 records i whose node_id is in that table with a table index < i
+ *   5  every other record, below
+ * reason[i], the first that applies:
+ *   1  DELETED flag set
+ *   2 / 4 / 3  exactly as the repair decides among them (a record with verdict NO_CHANNEL is 3), but against the FINAL announcements and
+ *      their node table: the amount record, the updates and the dying records of a stale channel, and the node_announcement of a node whose
+ *      channels are all stale, are 3
+ *   7  STALE: an announcement the repair would keep, by step 3 (every other announcement keeps the repair's reason)
+ *   6  TIMESTAMP: a 257 / 258 with verdict OK that is not eligible -- reported whether or not its dependencies are kept, in place of 3
+ *   5  SUPERSEDED: an eligible 257 / 258 with kept dependencies that is not the winner of its slot
+ *   0  kept
+ * So: a record whose verdict is not OK never supersedes anything; an update in front of its announcement never supersedes one behind it;
+ * with now == 0 neither the clock half of ELIGIBLE nor STALE applies; the output audits clean, the plain repair of it drops its uuid record
+ * alone, and this call on it with the same policy and uuid returns it unchanged. */
+typedef struct {
+	uint64_t now;            /* UNIX seconds; 0 = no clock: the FUTURE and the STALE rule are off */
+	uint32_t future_slack;   /* seconds a signed timestamp may lie ahead of now (the reference: 86 400) */
+	uint32_t prune_interval; /* seconds; 0 = the STALE rule is off (the reference: 1 209 600, common/gossip_constants.h:85) */
+} lamd_store_latest_policy;
+typedef struct {
+	uint64_t kept;
+	uint64_t dropped_deleted, dropped_verdict, dropped_dependency, dropped_bookkeeping,   /* reasons 1..4, as the repair */
+		 dropped_superseded, dropped_timestamp, dropped_stale;                         /* reasons 5..7 */
+	uint64_t out_len;
+	double stage_ms[3];      /* keep stages (all the new launches), scan, copy */
+} lamd_store_latest_summary;
+/* Every argument shared with lamd_gossip_store_repair keeps that call's meaning, return codes and sizes; the output has its format (version
+ * byte, uuid record, the kept records verbatim in file order) and is never longer than len + 46 bytes.  policy == NULL: LAMD_ERR_ARG.
+ * The device work is queued behind the audit's on the same stream, one lane per record, each stage a launch of its own because it reads
+ * what the one before wrote with atomics: k_store_latest_upd (eligibility, the update slots -- one 64-bit key ts << 32 | ~index per
+ * (announcement, direction), written with atomicMax -- and the dying marks), k_store_latest_chan (final announcements, node table),
+ * k_store_latest_node (the node slots), k_store_latest_rest (every other record); then the repair's scan, copy and two host waits.
+ * stage_ms (with lamd_set_timing): the four launches and the clearing of their tables; scan; copy. */
+int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32,
+				    const lamd_store_latest_policy *policy, size_t cap, uint64_t *rec_off, int8_t *verdict, uint64_t *new_off,
+				    uint8_t *reason, size_t *n_records, uint8_t *out, void *d_out, size_t out_cap,
+				    lamd_store_summary *summary, lamd_store_latest_summary *latest);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

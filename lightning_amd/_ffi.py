@@ -40,6 +40,18 @@ class LamdStoreRepairSummary(ctypes.Structure):
                 ("dropped_bookkeeping", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
 
 
+class LamdStoreLatestPolicy(ctypes.Structure):
+    """lamd_store_latest_policy (include/lightning_amd.h): the clock lamd_gossip_store_repair_latest judges timestamps by"""
+    _fields_ = [("now", ctypes.c_uint64), ("future_slack", ctypes.c_uint32), ("prune_interval", ctypes.c_uint32)]
+
+
+class LamdStoreLatestSummary(ctypes.Structure):
+    """lamd_store_latest_summary (include/lightning_amd.h): what lamd_gossip_store_repair_latest reports about the store it wrote"""
+    _fields_ = [("kept", ctypes.c_uint64), ("dropped_deleted", ctypes.c_uint64), ("dropped_verdict", ctypes.c_uint64), ("dropped_dependency", ctypes.c_uint64),
+                ("dropped_bookkeeping", ctypes.c_uint64), ("dropped_superseded", ctypes.c_uint64), ("dropped_timestamp", ctypes.c_uint64),
+                ("dropped_stale", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
+
+
 # name -> (restype, argtypes); every symbol of include/lightning_amd.h and include/lightning_amd_debug.h
 SYMBOLS = {
     "lamd_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
@@ -81,6 +93,9 @@ SYMBOLS = {
     "lamd_gossip_store_audit": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.POINTER(c_sz), ctypes.POINTER(LamdStoreSummary)]),
     "lamd_gossip_store_repair": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.POINTER(c_sz), c_u8p,
                                                 ctypes.c_void_p, c_sz, ctypes.POINTER(LamdStoreSummary), ctypes.POINTER(LamdStoreRepairSummary)]),
+    "lamd_gossip_store_repair_latest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_u8p, ctypes.POINTER(LamdStoreLatestPolicy), c_sz, c_u8p, c_u8p,
+                                                       c_u8p, c_u8p, ctypes.POINTER(c_sz), c_u8p, ctypes.c_void_p, c_sz, ctypes.POINTER(LamdStoreSummary),
+                                                       ctypes.POINTER(LamdStoreLatestSummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

@@ -23,6 +23,7 @@
 #include "key_column.h"
 #include "store_audit.h"
 #include "store_repair.h"
+#include "store_latest.h"
 
 using namespace lamd;
 
@@ -527,6 +528,51 @@ __global__ void __launch_bounds__(256) k_store_keep_rest(u32 n, const u8 *__rest
   if (store_is_live_cann(store, store_len, rec_off[i])) return;
   u32 sz;
   reason[i] = (u8)store_keep_other(store, store_len, rec_off, verdict, n, i, keys, vals, bits, nkeys, nvals, nbits, reason, &sz);
+  size[i] = sz;
+}
+// ---- the keep stages of the latest-wins repair (lamd_gossip_store_repair_latest; per-record logic in store_latest.h) in place of the two
+// kernels above.  Each reads what the one before it wrote with atomics (update slots and dying marks -> announcements and node table ->
+// node slots -> the rest), so each is a launch of its own: no workgroup waits for another.  latest: 2 * n slots, nlatest: 1 << nbits slots,
+// dying: n bytes, all preset to 0; nkeys / nvals as above.  Lane n of k_store_latest_rest writes the closing size 0.
+__global__ void __launch_bounds__(256) k_store_latest_upd(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                          const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
+                                                          u32 bits, lamd_store_latest_policy pol, u64 *latest, u8 *dying) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_latest_upd_one(store, store_len, rec_off, verdict, i, keys, vals, bits, pol, latest, dying);
+}
+__global__ void __launch_bounds__(256) k_store_latest_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                           const int8_t *__restrict__ verdict, lamd_store_latest_policy pol,
+                                                           const u64 *__restrict__ latest, const u8 *__restrict__ dying, u64 *nkeys, u32 *nvals,
+                                                           u32 nbits, u8 *__restrict__ reason, u32 *__restrict__ size) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !store_is_live_cann(store, store_len, rec_off[i])) return;
+  u32 sz;
+  u64 idoff = 0;
+  const u32 r = store_latest_cann_one(store, store_len, rec_off, verdict, n, i, pol, latest, dying, &sz, &idoff);
+  reason[i] = (u8)r;
+  size[i] = sz;
+  if (r == STORE_DROP_KEPT) {
+    store_node_insert(store, nkeys, nvals, nbits, idoff, i);
+    store_node_insert(store, nkeys, nvals, nbits, idoff + 33, i);
+  }
+}
+__global__ void __launch_bounds__(256) k_store_latest_node(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                           const int8_t *__restrict__ verdict, const u64 *__restrict__ nkeys,
+                                                           const u32 *__restrict__ nvals, u32 nbits, lamd_store_latest_policy pol, u64 *nlatest) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_latest_node_one(store, store_len, rec_off, verdict, i, nkeys, nvals, nbits, pol, nlatest);
+}
+__global__ void __launch_bounds__(256) k_store_latest_rest(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                           const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
+                                                           u32 bits, const u64 *__restrict__ nkeys, const u32 *__restrict__ nvals, u32 nbits,
+                                                           lamd_store_latest_policy pol, const u64 *__restrict__ latest,
+                                                           const u64 *__restrict__ nlatest, u8 *reason, u32 *__restrict__ size) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  if (i == n) { size[n] = 0; return; }
+  if (store_is_live_cann(store, store_len, rec_off[i])) return;
+  u32 sz;
+  reason[i] = (u8)store_latest_other_one(store, store_len, rec_off, verdict, n, i, keys, vals, bits, nkeys, nvals, nbits, reason, pol, latest, nlatest, &sz);
   size[i] = sz;
 }
 // The exclusive scan of the sizes, 64-bit, in tiles of STORE_SCAN_TILE = one block: k_store_scan_reduce leaves one sum per tile, the sums are
@@ -3975,16 +4021,104 @@ extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size
 
 // ---- gossip_store repair: the audit's stages, then keep flags, scan and copy on the same stream.  ONE wait more than the audit: the
 // verdicts, reasons, offsets and the output's length come down first (the length decides how much of the image follows).
-static void store_count_reasons(const uint8_t *reason, size_t n, lamd_store_repair_summary *r) {
-  for (size_t i = 0; i < n; i++) {
-    switch (reason[i]) {
-      case STORE_DROP_KEPT: r->kept++; break;
-      case STORE_DROP_DELETED: r->dropped_deleted++; break;
-      case STORE_DROP_VERDICT: r->dropped_verdict++; break;
-      case STORE_DROP_DEPENDENCY: r->dropped_dependency++; break;
-      default: r->dropped_bookkeeping++;
+// lamd_gossip_store_repair and lamd_gossip_store_repair_latest differ in their keep stages alone: what lies in front of them
+// (store_rep_plan, store_repair_empty) and behind them (store_repair_finish) is one piece of code.
+struct store_rep_plan {
+  std::vector<size_t> cnt;   // the scan's levels: cnt[0] = n + 1 sizes (the last one 0), cnt[k + 1] = the tiles of level k, until one tile holds a level
+  size_t n_sums = 0, nslots = 0, upper = 0;   // all tiles' sums; slots of the node table; no output is longer than `upper`
+  u32 nbits = 1;
+  store_rep_plan(size_t n, size_t n_cann, size_t len) : cnt{n + 1} {
+    while (cnt.back() > STORE_SCAN_TILE) cnt.push_back((cnt.back() + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE);
+    for (size_t k = 1; k < cnt.size(); k++) n_sums += cnt[k];
+    while (((size_t)1 << nbits) < 4 * n_cann) nbits++;
+    nslots = (size_t)1 << nbits;
+    upper = len + STORE_REPAIR_HEAD - 1;
+  }
+};
+struct store_rep_dev {   // where the keep stages left their results, and where the output goes
+  u64 *pos, *newoff, *sums;
+  u32 *size;
+  u8 *reason, *img_out;
+  size_t dev_cap;
+};
+// a store without any record: the version byte and the uuid record
+static int store_repair_empty(lamd_ctx *ctx, const store_head &head, int8_t *verdict, lamd_store_summary *summary, uint8_t *out, void *d_out, size_t out_cap,
+                              uint64_t *out_len) {
+  store_count_verdicts(verdict, 0, summary);
+  *out_len = STORE_REPAIR_HEAD;
+  if ((out || d_out) && out_cap < STORE_REPAIR_HEAD) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
+  if (out) memcpy(out, head.b, STORE_REPAIR_HEAD);
+  if (d_out) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpy(d_out, head.b, STORE_REPAIR_HEAD, hipMemcpyHostToDevice));
+  }
+  return LAMD_OK;
+}
+// Behind the keep stages (ev_rep[0] was recorded in front of them): the scan, the copy, the two waits.  counts[r] = records with reason r;
+// stage_ms: keep, scan, copy.  *out_len and the counts are set before the output's size is checked against out_cap.
+static int store_repair_finish(lamd_ctx *ctx, const store_job &job, size_t len, const store_rep_plan &plan, const store_rep_dev &d, const store_head &head,
+                               int8_t *verdict, uint64_t *new_off, uint8_t *reason, uint8_t *out, bool want_out, size_t out_cap,
+                               lamd_store_summary *summary, uint64_t counts[8], uint64_t *out_len, double stage_ms[3]) {
+  lamd_ctx *L = job.L;
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(L->stream);
+    if (L != ctx) ctx->err = L->err;
+    return code;
+  };
+  const size_t n = job.n;
+  const std::vector<size_t> &cnt = plan.cnt;
+  const bool timed = ctx->timing;
+  hipStream_t st = L->stream;
+  int rc;
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(L->ev_rep[1], st));
+  {
+    std::vector<u64 *> lvl{d.pos};   // level k >= 1 lives in d.sums and is scanned in place
+    for (size_t k = 1, o = 0; k < cnt.size(); o += cnt[k], k++) lvl.push_back(d.sums + o);
+    const size_t top = cnt.size() - 1;
+    for (size_t k = 0; k < top; k++) {
+      if (k == 0) hipLaunchKernelGGL(k_store_scan_reduce<u32>, dim3((unsigned)cnt[1]), dim3(256), 0, st, (u64)cnt[0], (const u32 *)d.size, lvl[1]);
+      else hipLaunchKernelGGL(k_store_scan_reduce<u64>, dim3((unsigned)cnt[k + 1]), dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], lvl[k + 1]);
+    }
+    for (size_t k = top + 1; k-- > 0;) {
+      const u64 *base = k == top ? nullptr : lvl[k + 1];
+      const dim3 grid((unsigned)((cnt[k] + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE));
+      if (k == 0) hipLaunchKernelGGL(k_store_scan_apply<u32>, grid, dim3(256), 0, st, (u64)cnt[0], (const u32 *)d.size, base, d.pos, (u64)n, (const u8 *)d.reason, d.newoff);
+      else hipLaunchKernelGGL(k_store_scan_apply<u64>, grid, dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], base, lvl[k], (u64)0, (const u8 *)nullptr, (u64 *)nullptr);
     }
   }
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(L->ev_rep[2], st));
+  if (want_out && d.dev_cap) {
+    const size_t words = (3 + (plan.upper < d.dev_cap ? plan.upper : d.dev_cap)) / 4 + 1;
+    hipLaunchKernelGGL(k_store_pack, dim3((unsigned)((words + STORE_PACK_WORDS - 1) / STORE_PACK_WORDS)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff,
+                       (const u64 *)d.pos, head, d.img_out, (u64)d.dev_cap);
+    STCHK(hipGetLastError());
+  }
+  if (timed) STCHK(hipEventRecord(L->ev_rep[3], st));
+  u64 payload = 0;
+  STCHK(hipMemcpyAsync(verdict, job.d_verdict, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(reason, d.reason, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(new_off, d.newoff, 8 * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&payload, d.pos + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed) {
+    if ((rc = store_audit_times(ctx, L, summary)) != LAMD_OK) return rc;
+    for (int k = 0; k < 3; k++) {
+      float ms = 0;
+      STCHK(hipEventElapsedTime(&ms, L->ev_rep[k], L->ev_rep[k + 1]));
+      stage_ms[k] = ms;
+    }
+  }
+  store_count_verdicts(verdict, n, summary);
+  for (size_t i = 0; i < n; i++) counts[reason[i] & 7]++;
+  *out_len = STORE_REPAIR_HEAD + payload;
+  if (want_out && *out_len > out_cap) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
+  if (out) {
+    STCHK(hipMemcpyAsync(out, d.img_out, *out_len, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));
+  }
+  return LAMD_OK;
 }
 extern "C" int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32, size_t cap,
                                         uint64_t *rec_off, int8_t *verdict, uint64_t *new_off, uint8_t *reason, size_t *n_records, uint8_t *out,
@@ -4001,34 +4135,18 @@ extern "C" int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, siz
   const store_head head = store_make_head(store[0], uuid32);
   const bool want_out = out || d_out;
   lamd_ctx *L = job.L;
-  if (!L) {   // no record: the version byte and the uuid record
-    store_count_verdicts(verdict, 0, summary);
-    repair->out_len = STORE_REPAIR_HEAD;
-    if (want_out && out_cap < STORE_REPAIR_HEAD) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
-    if (out) memcpy(out, head.b, STORE_REPAIR_HEAD);
-    if (d_out) {
-      HIPCHK(ctx, hipSetDevice(ctx->device));
-      HIPCHK(ctx, hipMemcpy(d_out, head.b, STORE_REPAIR_HEAD, hipMemcpyHostToDevice));
-    }
-    return LAMD_OK;
-  }
+  if (!L) return store_repair_empty(ctx, head, verdict, summary, out, d_out, out_cap, &repair->out_len);
   auto fail = [&](int code) {
     (void)hipStreamSynchronize(L->stream);
     if (L != ctx) ctx->err = L->err;
     return code;
   };
   const size_t n = job.n;
-  // the scan's levels: cnt[0] = n + 1 sizes (the last one 0), cnt[k + 1] = the tiles of level k, until one tile holds a level
-  std::vector<size_t> cnt{n + 1};
-  while (cnt.back() > STORE_SCAN_TILE) cnt.push_back((cnt.back() + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE);
-  size_t n_sums = 0;
-  for (size_t k = 1; k < cnt.size(); k++) n_sums += cnt[k];
-  u32 nbits = 1;
-  while (((size_t)1 << nbits) < 4 * job.n_cann) nbits++;
-  const size_t nslots = (size_t)1 << nbits, upper = len + STORE_REPAIR_HEAD - 1;   // upper: no output is longer
+  const store_rep_plan plan(n, job.n_cann, len);
+  const size_t n_sums = plan.n_sums, nslots = plan.nslots;
   // pos u64[n + 1] | new_off u64[n] | sums u64[n_sums] | nkeys u64[nslots] | nvals u32[nslots] | size u32[n + 1] | reason u8[n]
   if ((rc = ensure(L, &L->st_rep, 8 * (2 * n + 1 + n_sums + nslots) + 4 * (nslots + n + 1) + n + 16)) != LAMD_OK) return fail(rc);
-  if (want_out && !d_out && (rc = ensure(L, &L->st_pack, upper + 16)) != LAMD_OK) return fail(rc);
+  if (want_out && !d_out && (rc = ensure(L, &L->st_pack, plan.upper + 16)) != LAMD_OK) return fail(rc);
   const bool timed = ctx->timing;
   if (timed)
     for (auto &e : L->ev_rep)
@@ -4037,63 +4155,88 @@ extern "C" int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, siz
   u64 *d_pos = L->st_rep.as<u64>(), *d_newoff = d_pos + n + 1, *d_sums = d_newoff + n, *d_nkeys = d_sums + n_sums;
   u32 *d_nvals = (u32 *)(d_nkeys + nslots), *d_size = d_nvals + nslots;
   u8 *d_reason = (u8 *)(d_size + n + 1);
-  u8 *d_img_out = d_out ? (u8 *)d_out : L->st_pack.as<u8>();
-  const size_t dev_cap = d_out ? out_cap : upper;
+  const store_rep_dev dev{d_pos, d_newoff, d_sums, d_size, d_reason, d_out ? (u8 *)d_out : L->st_pack.as<u8>(), d_out ? out_cap : plan.upper};
   STCHK(hipMemsetAsync(d_nkeys, 0xFF, nslots * 12, st));
   if (timed) STCHK(hipEventRecord(L->ev_rep[0], st));
-  hipLaunchKernelGGL(k_store_keep_chan, dim3(blocks_for(n)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, d_nkeys, d_nvals, nbits,
+  hipLaunchKernelGGL(k_store_keep_chan, dim3(blocks_for(n)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, d_nkeys, d_nvals, plan.nbits,
                      d_reason, d_size);
   hipLaunchKernelGGL(k_store_keep_rest, dim3(blocks_for(n + 1)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals,
-                     job.bits, (const u64 *)d_nkeys, (const u32 *)d_nvals, nbits, d_reason, d_size);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(L->ev_rep[1], st));
-  {
-    std::vector<u64 *> lvl{d_pos};   // level k >= 1 lives in d_sums and is scanned in place
-    for (size_t k = 1, o = 0; k < cnt.size(); o += cnt[k], k++) lvl.push_back(d_sums + o);
-    const size_t top = cnt.size() - 1;
-    for (size_t k = 0; k < top; k++) {
-      if (k == 0) hipLaunchKernelGGL(k_store_scan_reduce<u32>, dim3((unsigned)cnt[1]), dim3(256), 0, st, (u64)cnt[0], (const u32 *)d_size, lvl[1]);
-      else hipLaunchKernelGGL(k_store_scan_reduce<u64>, dim3((unsigned)cnt[k + 1]), dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], lvl[k + 1]);
-    }
-    for (size_t k = top + 1; k-- > 0;) {
-      const u64 *base = k == top ? nullptr : lvl[k + 1];
-      const dim3 grid((unsigned)((cnt[k] + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE));
-      if (k == 0) hipLaunchKernelGGL(k_store_scan_apply<u32>, grid, dim3(256), 0, st, (u64)cnt[0], (const u32 *)d_size, base, d_pos, (u64)n, (const u8 *)d_reason, d_newoff);
-      else hipLaunchKernelGGL(k_store_scan_apply<u64>, grid, dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], base, lvl[k], (u64)0, (const u8 *)nullptr, (u64 *)nullptr);
-    }
+                     job.bits, (const u64 *)d_nkeys, (const u32 *)d_nvals, plan.nbits, d_reason, d_size);
+  uint64_t counts[8] = {};
+  rc = store_repair_finish(ctx, job, len, plan, dev, head, verdict, new_off, reason, out, want_out, out_cap, summary, counts, &repair->out_len, repair->stage_ms);
+  repair->kept = counts[STORE_DROP_KEPT];
+  repair->dropped_deleted = counts[STORE_DROP_DELETED];
+  repair->dropped_verdict = counts[STORE_DROP_VERDICT];
+  repair->dropped_dependency = counts[STORE_DROP_DEPENDENCY];
+  repair->dropped_bookkeeping = counts[STORE_DROP_BOOKKEEPING];
+  return rc;
+}
+
+// ---- latest-wins repair: the same call with four keep stages (store_latest.h) in place of two
+extern "C" int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32,
+                                               const lamd_store_latest_policy *policy, size_t cap, uint64_t *rec_off, int8_t *verdict, uint64_t *new_off,
+                                               uint8_t *reason, size_t *n_records, uint8_t *out, void *d_out, size_t out_cap,
+                                               lamd_store_summary *summary, lamd_store_latest_summary *latest) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!store || !uuid32 || !policy || !n_records || !summary || !latest || (cap && (!rec_off || !verdict || !new_off || !reason))) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
   }
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(L->ev_rep[2], st));
-  if (want_out && dev_cap) {
-    const size_t words = (3 + (upper < dev_cap ? upper : dev_cap)) / 4 + 1;
-    hipLaunchKernelGGL(k_store_pack, dim3((unsigned)((words + STORE_PACK_WORDS - 1) / STORE_PACK_WORDS)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff,
-                       (const u64 *)d_pos, head, d_img_out, (u64)dev_cap);
-    STCHK(hipGetLastError());
-  }
-  if (timed) STCHK(hipEventRecord(L->ev_rep[3], st));
-  u64 payload = 0;
-  STCHK(hipMemcpyAsync(verdict, job.d_verdict, n, hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(reason, d_reason, n, hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(new_off, d_newoff, 8 * n, hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(&payload, d_pos + n, 8, hipMemcpyDeviceToHost, st));
-  STCHK(hipStreamSynchronize(st));
-  if (timed) {
-    if ((rc = store_audit_times(ctx, L, summary)) != LAMD_OK) return rc;
-    for (int k = 0; k < 3; k++) {
-      float ms = 0;
-      STCHK(hipEventElapsedTime(&ms, L->ev_rep[k], L->ev_rep[k + 1]));
-      repair->stage_ms[k] = ms;
-    }
-  }
-  store_count_verdicts(verdict, n, summary);
-  store_count_reasons(reason, n, repair);
-  repair->out_len = STORE_REPAIR_HEAD + payload;
-  if (want_out && repair->out_len > out_cap) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
-  if (out) {
-    STCHK(hipMemcpyAsync(out, d_img_out, repair->out_len, hipMemcpyDeviceToHost, st));
-    STCHK(hipStreamSynchronize(st));
-  }
-  return LAMD_OK;
+  *latest = lamd_store_latest_summary();
+  const lamd_store_latest_policy pol = *policy;
+  store_job job;
+  int rc = store_audit_queue(ctx, store, len, d_store, cap, rec_off, n_records, summary, &job);
+  if (rc != LAMD_OK) return rc;
+  const store_head head = store_make_head(store[0], uuid32);
+  const bool want_out = out || d_out;
+  lamd_ctx *L = job.L;
+  if (!L) return store_repair_empty(ctx, head, verdict, summary, out, d_out, out_cap, &latest->out_len);
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(L->stream);
+    if (L != ctx) ctx->err = L->err;
+    return code;
+  };
+  const size_t n = job.n;
+  const store_rep_plan plan(n, job.n_cann, len);
+  const size_t n_sums = plan.n_sums, nslots = plan.nslots;
+  // pos u64[n + 1] | new_off u64[n] | sums u64[n_sums] | latest u64[2 n] | nlatest u64[nslots] | nkeys u64[nslots] | nvals u32[nslots] | size u32[n + 1] |
+  // reason u8[n] | dying u8[n]
+  if ((rc = ensure(L, &L->st_rep, 8 * (4 * n + 1 + n_sums + 2 * nslots) + 4 * (nslots + n + 1) + 2 * n + 16)) != LAMD_OK) return fail(rc);
+  if (want_out && !d_out && (rc = ensure(L, &L->st_pack, plan.upper + 16)) != LAMD_OK) return fail(rc);
+  const bool timed = ctx->timing;
+  if (timed)
+    for (auto &e : L->ev_rep)
+      if (!e) STCHK(hipEventCreate(&e));
+  hipStream_t st = L->stream;
+  u64 *d_pos = L->st_rep.as<u64>(), *d_newoff = d_pos + n + 1, *d_sums = d_newoff + n, *d_latest = d_sums + n_sums, *d_nlatest = d_latest + 2 * n,
+      *d_nkeys = d_nlatest + nslots;
+  u32 *d_nvals = (u32 *)(d_nkeys + nslots), *d_size = d_nvals + nslots;
+  u8 *d_reason = (u8 *)(d_size + n + 1), *d_dying = d_reason + n;
+  const store_rep_dev dev{d_pos, d_newoff, d_sums, d_size, d_reason, d_out ? (u8 *)d_out : L->st_pack.as<u8>(), d_out ? out_cap : plan.upper};
+  if (timed) STCHK(hipEventRecord(L->ev_rep[0], st));
+  STCHK(hipMemsetAsync(d_latest, 0, 8 * (2 * n + nslots), st));
+  STCHK(hipMemsetAsync(d_nkeys, 0xFF, nslots * 12, st));
+  STCHK(hipMemsetAsync(d_dying, 0, n, st));
+  const dim3 grid(blocks_for(n)), block(256);
+  hipLaunchKernelGGL(k_store_latest_upd, grid, block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals, job.bits, pol, d_latest,
+                     d_dying);
+  hipLaunchKernelGGL(k_store_latest_chan, grid, block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, pol, (const u64 *)d_latest, (const u8 *)d_dying,
+                     d_nkeys, d_nvals, plan.nbits, d_reason, d_size);
+  hipLaunchKernelGGL(k_store_latest_node, grid, block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, (const u64 *)d_nkeys, (const u32 *)d_nvals,
+                     plan.nbits, pol, d_nlatest);
+  hipLaunchKernelGGL(k_store_latest_rest, dim3(blocks_for(n + 1)), block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals,
+                     job.bits, (const u64 *)d_nkeys, (const u32 *)d_nvals, plan.nbits, pol, (const u64 *)d_latest, (const u64 *)d_nlatest, d_reason, d_size);
+  uint64_t counts[8] = {};
+  rc = store_repair_finish(ctx, job, len, plan, dev, head, verdict, new_off, reason, out, want_out, out_cap, summary, counts, &latest->out_len, latest->stage_ms);
+  latest->kept = counts[STORE_DROP_KEPT];
+  latest->dropped_deleted = counts[STORE_DROP_DELETED];
+  latest->dropped_verdict = counts[STORE_DROP_VERDICT];
+  latest->dropped_dependency = counts[STORE_DROP_DEPENDENCY];
+  latest->dropped_bookkeeping = counts[STORE_DROP_BOOKKEEPING];
+  latest->dropped_superseded = counts[STORE_DROP_SUPERSEDED];
+  latest->dropped_timestamp = counts[STORE_DROP_TIMESTAMP];
+  latest->dropped_stale = counts[STORE_DROP_STALE];
+  return rc;
 }
 #undef STCHK
 

@@ -51,6 +51,13 @@ def _repair_summary(r):
     return d
 
 
+def _latest_summary(r):
+    d = {k: int(getattr(r, k)) for k in ("kept", "dropped_deleted", "dropped_verdict", "dropped_dependency", "dropped_bookkeeping", "dropped_superseded",
+                                         "dropped_timestamp", "dropped_stale", "out_len")}
+    d["stage_ms"] = list(r.stage_ms)
+    return d
+
+
 def _store_blob(blob):
     a = np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, dtype=np.uint8)
     return a, a.size, (a if a.size else np.zeros(1, dtype=np.uint8))
@@ -331,11 +338,23 @@ class Engine:
         d_out: a torch uint8 CUDA tensor the output is left in (len(blob) + 46 bytes always suffice); host_out=False: no copy to the host.
         -> (out bytes or None, rec_off uint64 [records], verdict int8 [records], new_off uint64 [records] (2**64 - 1: dropped), reason uint8 [records],
             audit summary dict, repair summary dict)"""
+        return self._store_repair(None, blob, uuid, d_store, d_out, host_out)
+
+    def gossip_store_repair_latest(self, blob, uuid, now=0, future_slack=86400, prune_interval=1209600, d_store=None, d_out=None, host_out=True):
+        """lamd_gossip_store_repair_latest: gossip_store_repair, and of the node_announcements and channel_updates that pass it only the latest per node
+        and per (channel, direction); records whose header timestamp is not the signed one or lies more than future_slack seconds ahead of `now`
+        are dropped, and so are channels a direction of which has been silent for more than prune_interval seconds.  now=0: no clock (both rules
+        that need one are off).  Arguments and result as gossip_store_repair; reasons 5 superseded, 6 timestamp, 7 stale; the last dict is
+        lamd_store_latest_summary."""
+        return self._store_repair(_ffi.LamdStoreLatestPolicy(int(now), int(future_slack), int(prune_interval)), blob, uuid, d_store, d_out, host_out)
+
+    def _store_repair(self, policy, blob, uuid, d_store, d_out, host_out):
         _, n_bytes, buf = _store_blob(blob)
         uuid = np.frombuffer(bytes(uuid), dtype=np.uint8)
         if uuid.size != 32:
             raise ValueError("the uuid has 32 bytes")
-        cnt, s, r = ctypes.c_size_t(0), _ffi.LamdStoreSummary(), _ffi.LamdStoreRepairSummary()
+        cnt, s = ctypes.c_size_t(0), _ffi.LamdStoreSummary()
+        r = _ffi.LamdStoreRepairSummary() if policy is None else _ffi.LamdStoreLatestSummary()
         self._lib.lamd_gossip_store_frame(buf.ctypes.data, n_bytes, 0, None, ctypes.byref(cnt), ctypes.byref(s))   # the count; the repair reports every error itself
         n = cnt.value
         off, verdict = np.zeros(max(1, n), dtype=np.uint64), np.zeros(max(1, n), dtype=np.int8)
@@ -351,11 +370,16 @@ class Engine:
         if d_store is not None or d_out is not None:
             self._after_torch()
         out = np.zeros(out_cap, dtype=np.uint8) if host_out else None
-        self._chk(self._lib.lamd_gossip_store_repair(self._ctx, buf.ctypes.data, n_bytes, d_ptr, uuid.ctypes.data, n, off.ctypes.data, verdict.ctypes.data,
-                                                     new_off.ctypes.data, reason.ctypes.data, ctypes.byref(cnt), out.ctypes.data if host_out else None, d_out_ptr,
-                                                     out_cap, ctypes.byref(s), ctypes.byref(r)))
+        head = (self._ctx, buf.ctypes.data, n_bytes, d_ptr, uuid.ctypes.data)
+        tail = (n, off.ctypes.data, verdict.ctypes.data, new_off.ctypes.data, reason.ctypes.data, ctypes.byref(cnt), out.ctypes.data if host_out else None, d_out_ptr,
+                out_cap, ctypes.byref(s), ctypes.byref(r))
+        if policy is None:
+            self._chk(self._lib.lamd_gossip_store_repair(*head, *tail))
+        else:
+            self._chk(self._lib.lamd_gossip_store_repair_latest(*head, ctypes.byref(policy), *tail))
         k = cnt.value
-        return (out[:r.out_len].tobytes() if host_out else None, off[:k], verdict[:k], new_off[:k], reason[:k], _store_summary(s), _repair_summary(r))
+        return (out[:r.out_len].tobytes() if host_out else None, off[:k], verdict[:k], new_off[:k], reason[:k], _store_summary(s),
+                _repair_summary(r) if policy is None else _latest_summary(r))
 
     # ---- single-item veneers (reference semantics)
     def check_signed_hash(self, hash32, sig64, pubkey):

@@ -8,6 +8,12 @@ chosen per process: run once with --ways 4 and once with --ways 8.
 
 --repair adds lamd_gossip_store_repair over the same image (resident in, output left resident): the keep, scan and pack stages from HIP
 events, a plain device-to-device copy of out_len bytes timed the same way (the yardstick of k_store_pack), and the whole call next to the audit's.
+
+--latest measures lamd_gossip_store_repair_latest instead, on that store with replays mixed in (seeded): the header timestamp of every update
+is its signed one, and behind each update come 0-3 extra signed copies of its (channel, direction) -- a verbatim copy (equal timestamp) and
+further updates of the same slot from a second stretch of the generator's stream (lower or higher timestamps), as far as the stream holds
+any -- all updates then shuffled behind the announcements.  It reports the three stage_ms of the new call next to the plain repair's on the
+same store in the same process, and the run-to-run spread of the signature stage they are to be read against.
 """
 import argparse
 import json
@@ -21,6 +27,8 @@ ap.add_argument("--cann", type=int, default=150_000)
 ap.add_argument("--cupd", type=int, default=450_000)
 ap.add_argument("--runs", type=int, default=10)
 ap.add_argument("--repair", action="store_true")
+ap.add_argument("--latest", action="store_true")
+ap.add_argument("--seed", type=int, default=20)
 args = ap.parse_args()
 os.environ["LAMD_STORE_CRC_WAYS"] = str(args.ways)     # read once, at the first audit of the process
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
@@ -62,6 +70,66 @@ def spread(xs):
     xs = sorted(xs)
     return dict(min=round(xs[0], 3), median=round(xs[len(xs) // 2], 3), max=round(xs[-1], 3))
 
+
+def latest_bench(eng):
+    """the store with replays, then the plain and the latest-wins repair over it: one JSON line"""
+    rng = np.random.Generator(np.random.PCG64(args.seed))
+    w = make_gossip(eng, args.cann, 2 * args.cupd)        # update u depends on (seed, u) alone: the first cupd are the plain store's
+    cann = w.msgs[:args.cann * CANN_LEN].reshape(args.cann, CANN_LEN)
+    cupd = w.msgs[args.cann * CANN_LEN:args.cann * CANN_LEN + 2 * args.cupd * CUPD_LEN].reshape(2 * args.cupd, CUPD_LEN)
+    slot = (cupd[:, 98:106].astype(np.uint64) << (8 * np.arange(7, -1, -1, dtype=np.uint64))).sum(axis=1) * 2 + (cupd[:, 111] & 1)
+    pool = {}                                             # slot -> the second stretch's updates of it
+    for u in range(args.cupd, 2 * args.cupd):
+        pool.setdefault(int(slot[u]), []).append(u)
+    rows, extra = list(range(args.cupd)), rng.integers(0, 4, args.cupd)
+    hist = [0, 0, 0, 0]
+    for u in range(args.cupd):
+        more = ([u] + [pool[int(slot[u])].pop() for _ in range(min(int(extra[u]) - 1, len(pool.get(int(slot[u]), ()))))]) if extra[u] else []
+        hist[len(more)] += 1
+        rows += more
+    rows = np.array(rows)[rng.permutation(len(rows))]
+    ups = cupd[rows]
+    ts_u = (ups[:, 106:110].astype(np.uint32) << (8 * np.arange(3, -1, -1, dtype=np.uint32))).sum(axis=1).astype(np.uint32)
+    amount = np.zeros((args.cann, 10), dtype=np.uint8)
+    amount[:, 0], amount[:, 1], amount[:, 7] = 0x10, 0x05, 1
+    pairs = np.concatenate([records(cann, np.arange(args.cann, dtype=np.uint32) + 1_600_000_000), records(amount, np.zeros(args.cann, dtype=np.uint32))], axis=1)
+    image = np.concatenate([np.array([0x10], dtype=np.uint8), pairs.reshape(-1), records(ups, ts_u).reshape(-1)])
+    d_image = torch.from_numpy(image).cuda()
+    d_out = torch.zeros(image.size + 46, dtype=torch.uint8, device="cuda")
+    uuid = bytes(range(32))
+    torch.cuda.synchronize()
+    calls = dict(plain=lambda: eng.gossip_store_repair(image, uuid, d_store=d_image, d_out=d_out, host_out=False),
+                 latest=lambda: eng.gossip_store_repair_latest(image, uuid, now=0, d_store=d_image, d_out=d_out, host_out=False))
+    first = {k: f() for k, f in calls.items()}            # warm-up, and what the two calls say about the store
+    lat = first["latest"][6]
+    assert np.array_equal(first["plain"][2], first["latest"][2]), "the two repairs' verdicts differ"
+    fixed = d_out[:lat["out_len"]].cpu().numpy()          # (the latest call ran last)
+    _, _, s2 = eng.gossip_store_audit(fixed, d_store=d_out[:lat["out_len"]])
+    assert s2["clean"] == 1 and s2["records"] == lat["kept"] + 1, (s2, lat)
+    eng.set_timing(True)
+    stages, sig, wall = {k: [] for k in calls}, [], {k: [] for k in calls}
+    for _ in range(args.runs):
+        for k, f in calls.items():                        # alternating: both see the same box in the same state
+            t0 = time.perf_counter()
+            out = f()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+            stages[k].append(out[6]["stage_ms"])
+            sig.append(out[5]["stage_ms"][3])
+    eng.set_timing(False)
+    keep = {k: spread([st[0] for st in stages[k]]) for k in calls}
+    print(json.dumps(dict(
+        latest=True, seed=args.seed, records=int(first["plain"][5]["records"]), updates=int(len(rows)), extra_copies_per_update=hist, image_bytes=int(image.size),
+        runs=args.runs, plain={k: first["plain"][6][k] for k in ("kept", "dropped_verdict", "dropped_dependency", "out_len")},
+        latest_summary={k: x for k, x in lat.items() if k != "stage_ms"},
+        stage_ms={k: {n: spread([st[j] for st in stages[k]]) for j, n in enumerate(("keep", "scan", "pack"))} for k in calls},
+        call_timed_ms={k: spread(wall[k]) for k in calls}, signature_stage_ms=spread(sig), signature_stage_spread_ms=round(max(sig) - min(sig), 3),
+        keep_latest_minus_plain_ms=round(keep["latest"]["median"] - keep["plain"]["median"], 3))))
+
+
+if args.latest:
+    with Engine(0) as eng:
+        latest_bench(eng)
+    sys.exit(0)
 
 with Engine(0) as eng:
     w = make_gossip(eng, args.cann, args.cupd)
