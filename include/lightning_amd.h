@@ -214,6 +214,54 @@ int lamd_ecdsa_recover_batch(lamd_ctx *ctx, size_t n, const uint8_t *hash32, con
 int lamd_ecdsa_recover_batch_device(lamd_ctx *ctx, size_t n, const void *d_hash32, const void *d_sig64, const void *d_recid,
 				    void *d_pub33, void *d_ok);
 
+/* ---- the same two call sites FROM THEIR TEXT: the signature half of bolt11_decode() (common/bolt11.c:980-1062) and of checkmessage
+ * (lightningd/signmessage.c:148-198) as one device call each over strings.  Decoding (bech32 / zbase32), the 5-bit to 8-bit repacking, the hashing,
+ * the choice between recovery and verification under the invoice's `n` field and the curve work all run on the device, one lane per string; the
+ * front-end kernel (k_bolt11_front / k_checkmessage_front), the key-parse kernel over the `n` keys, the verification batch (rows with `n`), the
+ * recovery batch (rows without) and the merge are queued on one stream without the host waiting in between.
+ *
+ * lamd_bolt11_check_batch: string i = strs[off[i] .. off[i+1]) (off: n+1 entries), no terminator, exactly what bolt11_decode() would be handed: the
+ * caller has stripped any "lightning:" prefix.  No length cap.  status[i] is the FIRST of these that applies, in the reference's order:
+ *   -1 LAMD_B11_BAD_BECH32     bech32_decode() (common/bech32.c:94-155) refuses the string: shorter than 8; no separator (the LAST '1'), an empty
+ *                              hrp, fewer than 6 data characters; an hrp byte outside 33..126; a data byte with bit 7 set or outside the alphabet
+ *                              (both cases map); mixed case anywhere in the string; a final polymod other than 1 (bech32m is refused)
+ *   -2 LAMD_B11_BAD_PREFIX     the lower-cased hrp does not start with "ln"
+ *   -3 LAMD_B11_MALFORMED      framing or the `n` field.  D = the data values without the checksum: 7 of them are the 35-bit timestamp; while more
+ *                              than 104 remain: 1 tag, a 2-value length, that many values -- a length greater than what remains (signature
+ *                              included) is malformed; at the end exactly 104 must remain.  The first field with tag 19 (`n`) and length
+ *                              exactly 53 is the payee key: malformed if its 265th bit is set or its 33 bytes are no valid compressed key
+ *                              (pubkey_from_node_id).  A tag-19 field of another length, and every one behind the key, is skipped like any
+ *                              other field (pull_expected_length / unknown_field)
+ *   -4 LAMD_B11_BAD_RECID      byte 64 of the 65 signature bytes is above 3 (with an `n` field too)
+ *   -5 LAMD_B11_SIG_RANGE      r or s >= n (secp256k1_ecdsa_recoverable_signature_parse_compact)
+ *   -6 LAMD_B11_NO_KEY         no `n` field, and secp256k1_ecdsa_recover fails.  No low-S rule on this path
+ *   -7 LAMD_B11_BAD_SIGNATURE  an `n` field, and secp256k1_ecdsa_verify under it fails: the low-S rule applies, the recovery id is ignored
+ *    0 LAMD_B11_OK
+ * node_id33 + 33*i = the recovered key or the `n` key; zero unless the status is OK.  hash32 + 32*i (may be NULL) = SHA-256(lower-cased hrp ||
+ * the data values in front of the signature packed 5 -> 8 bits, the last byte padded with zero bits): the hash_u5 result; zero for statuses
+ * -1 .. -3.  have_n[i] (may be NULL) = 1 iff an `n` key was found; zero for statuses -1 .. -3.
+ * CONTRACT: fields other than `n` are walked and hashed, never interpreted -- chain name, amount, the required p / s / d|h fields, features,
+ * utf-8 and route keys stay bolt11_decode_nosig()'s job (:748-975).  For a string bolt11_decode() accepts the status is OK and the key is its
+ * receiver_id; for a string it rejects for one of the reasons above, with nothing unchecked failing earlier, the status is that reason. */
+enum { LAMD_B11_OK = 0, LAMD_B11_BAD_BECH32 = -1, LAMD_B11_BAD_PREFIX = -2, LAMD_B11_MALFORMED = -3,
+       LAMD_B11_BAD_RECID = -4, LAMD_B11_SIG_RANGE = -5, LAMD_B11_NO_KEY = -6, LAMD_B11_BAD_SIGNATURE = -7 };
+int lamd_bolt11_check_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off,
+			    int8_t *status, uint8_t *node_id33, uint8_t *hash32 /* may be NULL */, uint8_t *have_n /* may be NULL */);
+/* lamd_checkmessage_batch: message i = msgs[moff[i] .. moff[i+1]) (any bytes, none included), its signature string zbase[zoff[i] .. zoff[i+1]).
+ * status[i], the first that applies:
+ *   -1 LAMD_MSG_BAD_ZBASE   a character outside "ybndrfg8ejkmcpqxot1uwisza345h769" (case-sensitive), or a character count that is no multiple
+ *                           of 8: from_zbase32() returns NULL (:36-55)
+ *   -2 LAMD_MSG_BAD_LENGTH  the string decodes to other than 65 bytes (:173)
+ *   -3 LAMD_MSG_BAD_SIG     byte 0 - 31 is not in 0..3, or r or s >= n (:178-183).  The reference hands an out-of-range id to the library
+ *                           unchecked (the library's argument check then calls its illegal-argument callback); here it is a bad signature
+ *   -4 LAMD_MSG_NO_KEY      recovery fails over SHA256(SHA256("Lightning Signed Message:" || msg)) (:188-198)
+ *    0 LAMD_MSG_OK          node_id33 + 33*i holds the key (zero otherwise): the caller compares it with the claimed key or looks it up in the graph
+ * Both calls: n == 0 is LAMD_OK; a NULL input, status or node_id33 is LAMD_ERR_ARG; calls of more than the chunk size (lamd_set_chunk_rows) run their
+ * curve work chunk by chunk; with lamd_set_timing(ctx, 1) lamd_info.last_text_ms holds the device time of the front end and of what follows it. */
+enum { LAMD_MSG_OK = 0, LAMD_MSG_BAD_ZBASE = -1, LAMD_MSG_BAD_LENGTH = -2, LAMD_MSG_BAD_SIG = -3, LAMD_MSG_NO_KEY = -4 };
+int lamd_checkmessage_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *moff,
+			    const uint8_t *zbase, const uint64_t *zoff, int8_t *status, uint8_t *node_id33);
+
 /* grind_htlc_tx_fee() (onchaind/onchaind.c:388-438): find the feerate whose fee makes `sig64` (one remote HTLC signature,
  * one key) verify.  For feerate = min_feerate..max_feerate: fee = feerate * weight / 1000 (amount_tx_fee), equal consecutive
  * fees are tried once, fees above input_sat end the search; candidate = the transaction with output 0 paying
@@ -550,6 +598,7 @@ typedef struct {
 	int hw_queues_env;        /* GPU_MAX_HW_QUEUES as lamd_init() found it (0 = unset: the runtime's default of 4; < 16 costs overlap between the lanes) */
 	int queue_sets;           /* staging sets of the streaming queue = the most flushes that may be outstanding */
 	size_t last_flush_inplace_rows; /* rows the last lamd_flush() sent to the device straight from the callers' registered memory (queued in place, not copied) */
+	double last_text_ms[2];   /* with timing on: device time of the last lamd_bolt11_check_batch / lamd_checkmessage_batch -- the front-end kernel; key parse, curve work and merge */
 } lamd_info;
 int lamd_get_info(lamd_ctx *ctx, lamd_info *info);
 int lamd_get_lane_info(lamd_ctx *ctx, int lane, lamd_info *info); /* the last call that ran on lane 0 .. lanes-1 */

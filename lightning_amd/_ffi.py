@@ -23,7 +23,7 @@ class LamdInfo(ctypes.Structure):
                 ("last_suspect_rows", ctypes.c_size_t), ("cache_enabled", ctypes.c_int), ("cache_entries", ctypes.c_size_t),
                 ("cache_capacity", ctypes.c_size_t), ("cache_resets", ctypes.c_size_t),
                 ("keyed_ecmult_ms_sum", ctypes.c_double * 2), ("keyed_ecmult_launches", ctypes.c_size_t * 2), ("hw_queues_env", ctypes.c_int), ("queue_sets", ctypes.c_int),
-                ("last_flush_inplace_rows", ctypes.c_size_t)]
+                ("last_flush_inplace_rows", ctypes.c_size_t), ("last_text_ms", ctypes.c_double * 2)]
 
 
 class LamdStoreSummary(ctypes.Structure):
@@ -75,6 +75,8 @@ SYMBOLS = {
     "lamd_bolt12_merkle_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.c_char_p, ctypes.c_char_p, c_u8p, c_u8p, c_u8p]),
     "lamd_ecdsa_recover_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
     "lamd_ecdsa_recover_batch_device": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
+    "lamd_bolt11_check_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
+    "lamd_checkmessage_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
     "lamd_grind_htlc_tx_fee": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_sz, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                               ctypes.c_uint32, c_u8p, ctypes.c_uint8, ctypes.c_int, c_u8p, ctypes.POINTER(ctypes.c_uint32),
                                               ctypes.POINTER(ctypes.c_uint64)]),

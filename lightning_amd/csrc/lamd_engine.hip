@@ -24,6 +24,7 @@
 #include "store_audit.h"
 #include "store_repair.h"
 #include "store_latest.h"
+#include "bolt11.h"
 
 using namespace lamd;
 
@@ -412,6 +413,63 @@ __global__ void __launch_bounds__(64) k_bolt12_hash(size_t n, const u8 *__restri
 __global__ void __launch_bounds__(256) k_apply_gate(size_t n, const u8 *__restrict__ gate, u8 *__restrict__ ok) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && !gate[i]) ok[i] = 0;
+}
+
+// ---- text front ends, one string per lane (bolt11.h): the columns the recovery and verification launches behind them take.  A row belongs to the
+// recovery batch (no `n` key) or to the verification batch (`n` key) only with status 0 so far; for every other row the batch gets what its early
+// reject removes -- recovery id 0xFF, a zero signature -- so both batches run over all n rows and nothing is compacted.  A row without an `n` key
+// carries the generator as its key: the key-parse kernel and the verification batch see a valid point.
+__device__ __constant__ static const u8 TEXT_DUMMY_KEY[33] = {0x02, 0x79, 0xBE, 0x66, 0x7E, 0xF9, 0xDC, 0xBB, 0xAC, 0x55, 0xA0, 0x62, 0x95, 0xCE, 0x87, 0x0B, 0x07,
+                                                              0x02, 0x9B, 0xFC, 0xDB, 0x2D, 0xCE, 0x28, 0xD9, 0x59, 0xF2, 0x81, 0x5B, 0x16, 0xF8, 0x17, 0x98};
+__global__ void __launch_bounds__(64) k_bolt11_front(size_t n, const u8 *__restrict__ strs, const u64 *__restrict__ off, int8_t *__restrict__ pre,
+                                                     u8 *__restrict__ hash32, u8 *__restrict__ sig64, u8 *__restrict__ recid_rec, u8 *__restrict__ sig_ver,
+                                                     u8 *__restrict__ key33, u8 *__restrict__ have_n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u8 recid, hn;
+  const int st = bolt11_front_one(strs + off[i], (size_t)(off[i + 1] - off[i]), hash32 + 32 * i, sig64 + 64 * i, &recid, key33 + 33 * i, &hn);
+  pre[i] = (int8_t)st;
+  have_n[i] = hn;
+  recid_rec[i] = st == LAMD_B11_OK && !hn ? recid : 0xFF;
+  const bool ver = st == LAMD_B11_OK && hn;
+  for (int b = 0; b < 64; b++) sig_ver[64 * i + b] = ver ? sig64[64 * i + b] : 0;
+  if (!hn)
+    for (int b = 0; b < 33; b++) key33[33 * i + b] = TEXT_DUMMY_KEY[b];
+}
+__global__ void __launch_bounds__(64) k_checkmessage_front(size_t n, const u8 *__restrict__ msgs, const u64 *__restrict__ moff, const u8 *__restrict__ zb,
+                                                           const u64 *__restrict__ zoff, int8_t *__restrict__ pre, u8 *__restrict__ hash32,
+                                                           u8 *__restrict__ sig64, u8 *__restrict__ recid_rec) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u8 recid;
+  const int st = checkmessage_front_one(msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), zb + zoff[i], (size_t)(zoff[i + 1] - zoff[i]), hash32 + 32 * i,
+                                        sig64 + 64 * i, &recid);
+  pre[i] = (int8_t)st;
+  recid_rec[i] = st == LAMD_MSG_OK ? recid : 0xFF;
+}
+// status and key of a row from what the stages left.  have_n == nullptr (checkmessage): no row has a key of its own.  With one: an `n` key that is
+// no point is MALFORMED, in front of what the signature bytes say (the reference parses the key while it walks the fields), and takes the
+// row's hash with it.
+__global__ void __launch_bounds__(256) k_text_merge(size_t n, const int8_t *__restrict__ pre, u8 *__restrict__ have_n, const u8 *__restrict__ keyok,
+                                                    const u8 *__restrict__ ok_ver, const u8 *__restrict__ ok_rec, const u8 *__restrict__ pub_rec,
+                                                    const u8 *__restrict__ key33, u8 *__restrict__ hash32, int no_key, int8_t *__restrict__ status,
+                                                    u8 *__restrict__ node_id33) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool hn = have_n && have_n[i];
+  int st = pre[i];
+  if (hn && !keyok[i] && (st == LAMD_B11_OK || st == LAMD_B11_BAD_RECID || st == LAMD_B11_SIG_RANGE)) {
+    st = LAMD_B11_MALFORMED;
+    have_n[i] = 0;
+    for (int b = 0; b < 32; b++) hash32[32 * i + b] = 0;
+  }
+  if (st == 0) {
+    if (hn) st = ok_ver[i] == 1 ? 0 : LAMD_B11_BAD_SIGNATURE;
+    else st = ok_rec[i] == 1 ? 0 : no_key;
+  }
+  status[i] = (int8_t)st;
+  const u8 *src = hn ? key33 + 33 * i : pub_rec + 33 * i;
+  for (int b = 0; b < 33; b++) node_id33[33 * i + b] = st == 0 ? src[b] : 0;
 }
 
 // ---- fee grind (verify_core.h "fee grind"): one thread prepares, one thread per candidate feerate
@@ -1761,6 +1819,9 @@ struct lamd_ctx {
   hipEvent_t ev_store[6] = {};                      // ... and its stage boundaries (created when a timed audit first runs)
   devbuf st_rep, st_pack;                           // gossip_store repair: reasons, sizes, offsets, block sums, node table; the output image
   hipEvent_t ev_rep[4] = {};                        // ... and its stage boundaries
+  devbuf tx_cols;                                   // text front ends (lamd_bolt11_check_batch, lamd_checkmessage_batch): the per-row columns
+  hipEvent_t ev_text[3] = {};                       // ... in front of the front-end kernel, behind it, behind the merge (created when a timed call first runs)
+  double text_ms[2] = {0, 0};                       // ... and what they measured last: front end, curve work + merge
   // timing
   bool timing = false;
   bool ev_recorded = false;
@@ -2143,8 +2204,10 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
   for (devbuf *b : {&ctx->small_done, &ctx->recs, &ctx->qwords, &ctx->keyok, &ctx->slots, &ctx->vbuf, &ctx->in_a, &ctx->in_b, &ctx->in_c, &ctx->out,
                     &ctx->g_msgs, &ctx->g_off, &ctx->g_ids, &ctx->g_rowbase, &ctx->g_hash, &ctx->g_sig, &ctx->g_pub,
                     &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict, &ctx->st_img, &ctx->st_host, &ctx->st_ids, &ctx->st_tab, &ctx->st_out, &ctx->st_rep,
-                    &ctx->st_pack})
+                    &ctx->st_pack, &ctx->tx_cols})
     release(b);
+  for (auto &e : ctx->ev_text)
+    if (e) (void)hipEventDestroy(e);
   for (auto &e : ctx->ev_store)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : ctx->ev_rep)
@@ -2352,6 +2415,7 @@ static int get_info_of(lamd_ctx *ctx, lamd_info *info) {
   info->hw_queues_env = hw_queues_from_env();
   info->queue_sets = QUEUE_SETS;
   info->last_flush_inplace_rows = root->last_flush_inplace_rows;
+  for (int i = 0; i < 2; i++) info->last_text_ms[i] = root->text_ms[i];
   for (int i = 0; i < 4; i++) info->last_kernel_ms[i] = ctx->last_ms[i];
   for (int i = 0; i < 2; i++) {
     info->keyed_ecmult_ms_sum[i] = self->keyed_ms_sum[i];
@@ -3726,6 +3790,141 @@ extern "C" int lamd_ecdsa_recover_batch(lamd_ctx *ctx, size_t n, const uint8_t *
   HIPCHK(ctx, hipMemcpyAsync(pub33, d_keys, n * 33, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ok, ctx->out.p, n, hipMemcpyDeviceToHost, ctx->stream));
   return lamd_synchronize(ctx);
+}
+
+// ---- signatures from their text: BOLT #11 invoices and signed messages (bolt11.h).  The front-end kernel, the key-parse kernel, the verification
+// batch, the recovery batch and the merge are queued on the context's stream without the host waiting in between; both batches run over all
+// n rows (k_bolt11_front on how the rows that do not belong to a batch leave it at once).
+struct text_cols {
+  int8_t *pre, *status;
+  u8 *hash, *sig, *sig_ver, *key, *recid_rec, *have_n, *keyok, *ok_ver, *ok_rec, *pub_rec, *node_id;
+  u32 *qwords;
+};
+static size_t text_cols_bytes(size_t n) { return n * (64 + 32 + 64 + 64 + 33 + 33 + 33 + 7) + 64; }
+static text_cols text_cols_at(u8 *p, size_t n) {
+  text_cols c;
+  c.qwords = (u32 *)p; p += 64 * n;     // what k_keys writes next to keyok (16-byte aligned: uint4 stores); never read
+  c.hash = p; p += 32 * n;              // 4-byte aligned
+  c.sig = p; p += 64 * n;
+  c.sig_ver = p; p += 64 * n;
+  c.key = p; p += 33 * n;
+  c.pub_rec = p; p += 33 * n;
+  c.node_id = p; p += 33 * n;
+  c.pre = (int8_t *)p; p += n;
+  c.status = (int8_t *)p; p += n;
+  c.recid_rec = p; p += n;
+  c.have_n = p; p += n;
+  c.keyok = p; p += n;
+  c.ok_ver = p; p += n;
+  c.ok_rec = p;
+  return c;
+}
+// strings back to back on the device, offsets relative to the first; `rel` must outlive the copies
+static int text_upload(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, devbuf *d_strs, size_t at, u64 *d_off, std::vector<u64> &rel) {
+  const size_t total = (size_t)(off[n] - off[0]);
+  rel.resize(n + 1);
+  for (size_t i = 0; i <= n; i++) {
+    if (off[i] < off[0] || (i && off[i] < off[i - 1])) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
+    rel[i] = off[i] - off[0] + at;
+  }
+  if (total) HIPCHK(ctx, hipMemcpyAsync(d_strs->as<u8>() + at, strs + off[0], total, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_off, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  return LAMD_OK;
+}
+static int text_timing_begin(lamd_ctx *ctx) {
+  if (!ctx->timing) return LAMD_OK;
+  for (auto &e : ctx->ev_text)
+    if (!e) HIPCHK(ctx, hipEventCreate(&e));
+  HIPCHK(ctx, hipEventRecord(ctx->ev_text[0], ctx->stream));
+  return LAMD_OK;
+}
+static int text_timing_end(lamd_ctx *ctx) {   // behind the synchronisation that ends the call
+  if (!ctx->timing) return LAMD_OK;
+  for (int k = 0; k < 2; k++) {
+    float ms = 0;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev_text[k], ctx->ev_text[k + 1]));
+    ctx->text_ms[k] = ms;
+  }
+  return LAMD_OK;
+}
+extern "C" int lamd_bolt11_check_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, int8_t *status, uint8_t *node_id33,
+                                       uint8_t *hash32, uint8_t *have_n) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (n == 0) return LAMD_OK;
+  if (!strs || !off || !status || !node_id33) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
+  if (off[n] < off[0]) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
+  if ((rc = ensure(ctx, &ctx->g_msgs, (size_t)(off[n] - off[0]) + 64)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->g_off, (n + 1) * 8)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->tx_cols, text_cols_bytes(n))) != LAMD_OK) return rc;
+  const text_cols c = text_cols_at(ctx->tx_cols.as<u8>(), n);
+  std::vector<u64> rel;   // the queued copy reads it: lives until the stream has been synchronised
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return code;
+  };
+  if ((rc = text_upload(ctx, n, strs, off, &ctx->g_msgs, 0, ctx->g_off.as<u64>(), rel)) != LAMD_OK) return fail(rc);
+  if ((rc = text_timing_begin(ctx)) != LAMD_OK) return fail(rc);
+  hipLaunchKernelGGL(k_bolt11_front, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(), c.pre,
+                     c.hash, c.sig, c.recid_rec, c.sig_ver, c.key, c.have_n);
+  if (ctx->timing && hipEventRecord(ctx->ev_text[1], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
+  // the key-parse kernel for its validity byte alone (its affine words in c.qwords are not read again): the verification batch parses the keys it
+  // needs once more, but reports validity only for the rows its early reject lets through, and a bad `n` key counts whatever the signature bytes are
+  hipLaunchKernelGGL(k_keys, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const u8 *)c.key, 33, (size_t)33, (const u32 *)nullptr, c.qwords, c.keyok,
+                     (const u32 *)nullptr);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return fail(LAMD_ERR_HIP); }
+  if ((rc = run_device(ctx, MODE_ECDSA, n, c.hash, c.sig_ver, c.key, 33, 33, c.ok_ver)) != LAMD_OK) return fail(rc);
+  if ((rc = recover_device(ctx, n, c.hash, c.sig, c.recid_rec, c.pub_rec, c.ok_rec)) != LAMD_OK) return fail(rc);
+  hipLaunchKernelGGL(k_text_merge, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const int8_t *)c.pre, c.have_n, (const u8 *)c.keyok, (const u8 *)c.ok_ver,
+                     (const u8 *)c.ok_rec, (const u8 *)c.pub_rec, (const u8 *)c.key, c.hash, (int)LAMD_B11_NO_KEY, c.status, c.node_id);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text merge: launch failed"; return fail(LAMD_ERR_HIP); }
+  if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
+  hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(node_id33, c.node_id, n * 33, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && hash32) e = hipMemcpyAsync(hash32, c.hash, n * 32, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && have_n) e = hipMemcpyAsync(have_n, c.have_n, n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
+  if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
+  return text_timing_end(ctx);
+}
+extern "C" int lamd_checkmessage_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *moff, const uint8_t *zbase, const uint64_t *zoff,
+                                       int8_t *status, uint8_t *node_id33) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (n == 0) return LAMD_OK;
+  if (!msgs || !moff || !zbase || !zoff || !status || !node_id33) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if (moff[n] < moff[0] || zoff[n] < zoff[0]) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
+  const size_t mbytes = (size_t)(moff[n] - moff[0]), zbytes = (size_t)(zoff[n] - zoff[0]);
+  if ((rc = ensure(ctx, &ctx->g_msgs, mbytes + zbytes + 64)) != LAMD_OK) return rc;   // messages | signature strings
+  if ((rc = ensure(ctx, &ctx->g_off, 2 * (n + 1) * 8)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->tx_cols, text_cols_bytes(n))) != LAMD_OK) return rc;
+  const text_cols c = text_cols_at(ctx->tx_cols.as<u8>(), n);
+  std::vector<u64> mrel, zrel;
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return code;
+  };
+  u64 *d_moff = ctx->g_off.as<u64>(), *d_zoff = d_moff + n + 1;
+  if ((rc = text_upload(ctx, n, msgs, moff, &ctx->g_msgs, 0, d_moff, mrel)) != LAMD_OK) return fail(rc);
+  if ((rc = text_upload(ctx, n, zbase, zoff, &ctx->g_msgs, mbytes, d_zoff, zrel)) != LAMD_OK) return fail(rc);
+  if ((rc = text_timing_begin(ctx)) != LAMD_OK) return fail(rc);
+  hipLaunchKernelGGL(k_checkmessage_front, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), (const u64 *)d_moff,
+                     ctx->g_msgs.as<const u8>(), (const u64 *)d_zoff, c.pre, c.hash, c.sig, c.recid_rec);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return fail(LAMD_ERR_HIP); }
+  if (ctx->timing && hipEventRecord(ctx->ev_text[1], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
+  if ((rc = recover_device(ctx, n, c.hash, c.sig, c.recid_rec, c.pub_rec, c.ok_rec)) != LAMD_OK) return fail(rc);
+  hipLaunchKernelGGL(k_text_merge, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const int8_t *)c.pre, (u8 *)nullptr, (const u8 *)nullptr, (const u8 *)nullptr,
+                     (const u8 *)c.ok_rec, (const u8 *)c.pub_rec, (const u8 *)nullptr, c.hash, (int)LAMD_MSG_NO_KEY, c.status, c.node_id);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text merge: launch failed"; return fail(LAMD_ERR_HIP); }
+  if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
+  hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(node_id33, c.node_id, n * 33, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
+  if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
+  return text_timing_end(ctx);
 }
 
 // ---- fee grind: see k_grind.  Returns 1 (found; *feerate, *fee set), 0 (no candidate verifies) or an error < 0.

@@ -261,6 +261,31 @@ class Engine:
                                                          keys.ctypes.data, ok.ctypes.data))
         return keys, ok.astype(bool)
 
+    def bolt11_check(self, strings):
+        """strings: BOLT #11 invoices as bolt11_decode() takes them (str or bytes, no "lightning:" prefix) -> (status int8 [n] (LAMD_B11_*),
+        node_id uint8 [n,33], hash uint8 [n,32], have_n bool [n]): decoding, hashing, recovery or verification under the `n` key on the device
+        (lamd_bolt11_check_batch)"""
+        blob, off = self._streams([x.encode("latin-1") if isinstance(x, str) else x for x in strings])
+        n = len(strings)
+        status, node, h, hn = np.zeros(n, dtype=np.int8), np.zeros((n, 33), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._chk(self._lib.lamd_bolt11_check_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, status.ctypes.data, node.ctypes.data, h.ctypes.data,
+                                                    hn.ctypes.data))
+        return status, node, h, hn.astype(bool)
+
+    def checkmessage(self, messages, zbases):
+        """messages, zbases: the message and the zbase32 signature string of each checkmessage call (str or bytes) -> (status int8 [n] (LAMD_MSG_*),
+        node_id uint8 [n,33]: the recovered key) (lamd_checkmessage_batch)"""
+        enc = lambda xs: [x.encode("utf-8") if isinstance(x, str) else x for x in xs]
+        if len(messages) != len(zbases):
+            raise ValueError("one signature string per message")
+        mblob, moff = self._streams(enc(messages))
+        zblob, zoff = self._streams(enc(zbases))
+        n = len(messages)
+        status, node = np.zeros(n, dtype=np.int8), np.zeros((n, 33), dtype=np.uint8)
+        self._chk(self._lib.lamd_checkmessage_batch(self._ctx, n, mblob.ctypes.data, moff.ctypes.data, zblob.ctypes.data, zoff.ctypes.data, status.ctypes.data,
+                                                    node.ctypes.data))
+        return status, node
+
     def _after_torch(self):
         """order the next submission after what torch's current stream holds (the tensors handed to the *_device methods are
         usually produced there); a device-side event, no host synchronisation.  The caller still has to keep the tensors alive
@@ -567,7 +592,7 @@ class Engine:
                     last_suspect_rows=inf.last_suspect_rows, cache_enabled=bool(inf.cache_enabled), cache_entries=inf.cache_entries,
                     cache_capacity=inf.cache_capacity, cache_resets=inf.cache_resets,
                     keyed_ecmult_ms_sum=list(inf.keyed_ecmult_ms_sum), keyed_ecmult_launches=list(inf.keyed_ecmult_launches), hw_queues_env=int(inf.hw_queues_env), queue_sets=int(inf.queue_sets),
-                    last_flush_inplace_rows=int(inf.last_flush_inplace_rows))
+                    last_flush_inplace_rows=int(inf.last_flush_inplace_rows), last_text_ms=list(inf.last_text_ms))
 
     def set_chunk_rows(self, rows):
         """lamd_set_chunk_rows: rows per launch sequence of the calls that follow (0 = default 2^22)"""
