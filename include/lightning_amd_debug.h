@@ -28,8 +28,37 @@ int lamd_x2_debug(lamd_ctx *ctx, char *report, size_t cap); /* diagnostic: a^3 i
 
 /* Diagnostic: copy nbytes at offset of internal work buffer `which` (0 prep records, 1 per-row key validity,
  * 2 dedupe representative, 3 dedupe uid, 4 key id per row, 5 first row of each distinct key, 6 distinct-key
- * validity, 7 distinct-key affine words, 8 key tables) to host memory.  Tests only. */
+ * validity, 7 distinct-key affine words, 8 the 7-tooth key tables (cache pool7), 9 the static G table -- any slice of its 11 GiB, 10 the 10-tooth key
+ * tables (cache pool10), 11 the key cache's entries: 20 words each -- 17 of key bytes (little-endian packed, word 16 = byte 64 | length << 8), meta
+ * (teeth 7 / 10, 0 = the key does not parse; | lane << 8), publication sequence number, table slot in the pool of its shape) to host memory.
+ * LAMD_ERR_ARG if offset + nbytes runs past the buffer.  Tests only. */
 int lamd_debug_read(lamd_ctx *ctx, int which, size_t offset, size_t nbytes, void *out);
+
+/* Diagnostic: judge every entry of [first, first + count) of the static G table (flat index = window << 24 | digit; entry = d * 2^(24 w) * G as
+ * x | y, 8 little-endian words each) on the device, from field multiplications alone -- no group-law code, no inversion, nothing the builder
+ * ran.  Entry i is proved from entry i - 1 and the window's entry 1 (entry 1 of a window from the previous window's last and first entries, entry 1
+ * of window 0 from the constant G), so a clean audit of the whole table proves every entry, and ONE wrong entry is reported at itself and at its
+ * successor.  d_image (device memory, may be NULL): a replacement for exactly the entries of the range -- entry first + k is read from
+ * d_image + 64 k, everything outside the range from the engine's own table.  Returns LAMD_ERR_ARG for a range that leaves the table. */
+enum {
+	LAMD_GTA_ZERO = 1,        /* the digit-0 entry is not all zero */
+	LAMD_GTA_NONCANON = 2,    /* a coordinate's words read as an integer >= p */
+	LAMD_GTA_OFF_CURVE = 4,   /* y^2 != x^3 + 7 */
+	LAMD_GTA_ANCHOR = 8,      /* entry 1 of window 0 is not G */
+	LAMD_GTA_X = 16,          /* the x relation of the chord / tangent rule fails */
+	LAMD_GTA_Y = 32,          /* the y relation fails */
+	LAMD_GTA_DEGENERATE = 64  /* the rule's operands coincide (x1 = x_B) or y_B = 0: they cannot be the points the rule needs */
+};
+#define LAMD_GTA_LIST 64
+typedef struct lamd_gtable_audit_result {
+	uint64_t bad;            /* number of bad entries in the range */
+	uint64_t first_bad;      /* lowest bad index (meaningful if bad != 0) ... */
+	uint32_t first_reason;   /* ... and its reason mask (LAMD_GTA_*) */
+	uint32_t n_list;         /* min(bad, LAMD_GTA_LIST) pairs follow, in no particular order */
+	uint64_t list_index[LAMD_GTA_LIST];
+	uint32_t list_reason[LAMD_GTA_LIST];
+} lamd_gtable_audit_result;
+int lamd_debug_gtable_audit(lamd_ctx *ctx, size_t first, size_t count, const void *d_image, lamd_gtable_audit_result *out);
 
 /* Measurement aid for bench.py's roofline block: the chip's sustained issue rate of the 32x32->64 multiply-add (v_mad_u64_u32 with an
  * SGPR carry-out, dependency-free, eight accumulators per lane) at `waves_per_simd` (1..8) waves per SIMD over `launches` launches of at least

@@ -52,6 +52,12 @@ class LamdStoreLatestSummary(ctypes.Structure):
                 ("dropped_stale", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
 
 
+class LamdGtableAuditResult(ctypes.Structure):
+    """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
+    _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
+                ("list_index", ctypes.c_uint64 * 64), ("list_reason", ctypes.c_uint32 * 64)]
+
+
 # name -> (restype, argtypes); every symbol of include/lightning_amd.h and include/lightning_amd_debug.h
 SYMBOLS = {
     "lamd_init": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
@@ -103,6 +109,7 @@ SYMBOLS = {
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),
     "lamd_x2_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),
     "lamd_debug_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_sz, c_sz, c_u8p]),
+    "lamd_debug_gtable_audit": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_sz, ctypes.c_void_p, ctypes.POINTER(LamdGtableAuditResult)]),
     "lamd_debug_mul32_peak": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 3),
     "lamd_debug_gtable": (ctypes.c_void_p, [ctypes.c_void_p]),
     "lamd_fuzz_field": (ctypes.c_int, [ctypes.c_void_p, c_sz, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, c_sz]),

@@ -25,6 +25,7 @@
 #include "store_repair.h"
 #include "store_latest.h"
 #include "bolt11.h"
+#include "table_audit.h"
 
 using namespace lamd;
 
@@ -5138,7 +5139,7 @@ extern "C" int lamd_selftest(lamd_ctx *ctx, const uint8_t *hash32, const uint8_t
       gtable_compute_entry(e, base, d);
       if (memcmp(e, &gt[(size_t)d * GT_ENTRY_WORDS], GT_ENTRY_WORDS * 4)) { fails |= 1 << 20; rep += "gtable w0 d=" + std::to_string(d) + " differs; "; }
     }
-    // window 1 entry 1 must equal 65536*G = window 0 ... (2^16)G: check via doubling
+    // window 1 entry 1 must equal 2^GTABLE_WINDOW_BITS * G (2^24 * G in the shipped build): check via doubling
     gej bb = gej_from_ge(ge_from_words(base, base + 8));
     for (int i = 0; i < GTABLE_WINDOW_BITS; i++) bb = gej_double(bb);
     const fe zi = fe_inv(fe_norm_weak(bb.z)); const fe zi2 = fe_sqr(zi);
@@ -5460,13 +5461,81 @@ extern "C" int lamd_debug_mul32_peak(lamd_ctx *ctx, int waves_per_simd, double m
 extern "C" const void *lamd_debug_gtable(lamd_ctx *ctx) { return ctx ? (const void *)ctx->gtable : nullptr; }
 extern "C" int lamd_debug_read(lamd_ctx *ctx, int which, size_t offset, size_t nbytes, void *out) {
   if (!ctx || !out) return LAMD_ERR_ARG;
-  devbuf *bufs[] = {&ctx->recs, &ctx->keyok, &ctx->kd_rep, &ctx->kd_uid, &ctx->row_ent, &ctx->kd_uniq, &ctx->hk[0].keyok, &ctx->hk[0].qwords, &ctx->cache_store.pool7};
-  if (which < 0 || which >= (int)(sizeof(bufs) / sizeof(bufs[0])) || !bufs[which]->p || offset + nbytes > bufs[which]->cap) {
+  const lamd_ctx::key_cache &kc = ctx->cache_store;
+  const devbuf gt = {ctx->gtable, ctx->gtable ? GTABLE_BYTES : 0};   // not a devbuf of the context: the table is shared by the device's engines
+  const devbuf *bufs[] = {&ctx->recs, &ctx->keyok, &ctx->kd_rep, &ctx->kd_uid, &ctx->row_ent, &ctx->kd_uniq, &ctx->hk[0].keyok, &ctx->hk[0].qwords, &kc.pool7,
+                          &gt, &kc.pool10, &kc.ents};
+  if (which < 0 || which >= (int)(sizeof(bufs) / sizeof(bufs[0])) || !bufs[which]->p || offset > bufs[which]->cap || nbytes > bufs[which]->cap - offset) {
     ctx->err = "debug_read: no such buffer / out of range";
     return LAMD_ERR_ARG;
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   HIPCHK(ctx, hipMemcpy(out, (const u8 *)bufs[which]->p + offset, nbytes, hipMemcpyDeviceToHost));
+  return LAMD_OK;
+}
+
+// ---- audit of the static G table (table_audit.h): one thread per entry of [first, first + count); a bad entry bumps the count, competes for the
+// lowest (index << 8 | reason) and, while there is room, leaves its (index, reason) pair in the report list
+struct gt_audit_dev {
+  unsigned long long lowest;   // (index << 8 | reason) of the lowest bad entry; all ones = none
+  u32 bad;
+  u32 pad;
+  unsigned long long list_index[LAMD_GTA_LIST];
+  u32 list_reason[LAMD_GTA_LIST];
+};
+static_assert(GTABLE_ENTRIES < ((size_t)1 << 32), "bad-entry count and list position are 32-bit");
+static_assert(GTA_ZERO == LAMD_GTA_ZERO && GTA_NONCANON == LAMD_GTA_NONCANON && GTA_OFF_CURVE == LAMD_GTA_OFF_CURVE && GTA_ANCHOR == LAMD_GTA_ANCHOR &&
+              GTA_X == LAMD_GTA_X && GTA_Y == LAMD_GTA_Y && GTA_DEGENERATE == LAMD_GTA_DEGENERATE, "table_audit.h and the debug header name the same bits");
+__global__ void __launch_bounds__(256) k_gtable_audit(gt_view v, gt_audit_dev *__restrict__ res) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= v.count) return;
+  const size_t idx = v.first + k;
+  const u32 reason = gtable_audit_entry(v, idx);
+  if (reason == 0) return;
+  const u32 pos = atomicAdd(&res->bad, 1u);
+  atomicMin(&res->lowest, ((unsigned long long)idx << 8) | reason);
+  if (pos < (u32)LAMD_GTA_LIST) {
+    res->list_index[pos] = idx;
+    res->list_reason[pos] = reason;
+  }
+}
+extern "C" int lamd_debug_gtable_audit(lamd_ctx *ctx, size_t first, size_t count, const void *d_image, lamd_gtable_audit_result *out) {
+  if (!ctx || !out) return LAMD_ERR_ARG;
+  if (!ctx->gtable || first > GTABLE_ENTRIES || count > GTABLE_ENTRIES - first) {
+    ctx->err = "gtable_audit: range outside the table";
+    return LAMD_ERR_ARG;
+  }
+  memset(out, 0, sizeof(*out));
+  if (count == 0) return LAMD_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  gt_audit_dev *d_res = nullptr;
+  HIPCHK(ctx, hipMalloc(&d_res, sizeof(gt_audit_dev)));
+  gt_audit_dev h;
+  memset(&h, 0, sizeof(h));
+  h.lowest = ~0ull;
+  hipError_t e = hipMemcpyAsync(d_res, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    const gt_view v = {(const u32 *)ctx->gtable, (const u32 *)d_image, first, count};
+    hipLaunchKernelGGL(k_gtable_audit, dim3(blocks_for(count)), dim3(256), 0, ctx->stream, v, d_res);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, d_res, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_res);
+  if (e != hipSuccess) {
+    ctx->err = std::string("gtable_audit: ") + hipGetErrorString(e);
+    return LAMD_ERR_HIP;
+  }
+  out->bad = h.bad;
+  if (h.bad) {
+    out->first_bad = h.lowest >> 8;
+    out->first_reason = (uint32_t)(h.lowest & 0xFFu);
+  }
+  out->n_list = h.bad < (u32)LAMD_GTA_LIST ? h.bad : (u32)LAMD_GTA_LIST;
+  for (uint32_t i = 0; i < out->n_list; i++) {
+    out->list_index[i] = h.list_index[i];
+    out->list_reason[i] = h.list_reason[i];
+  }
   return LAMD_OK;
 }

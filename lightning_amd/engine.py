@@ -542,6 +542,31 @@ class Engine:
         rc = self._chk(self._lib.lamd_fuzz_field(self._ctx, lanes, iters, seed, ctypes.byref(ops), buf, 4096))
         return rc, ops.value, buf.value.decode()
 
+    # lamd_debug_read's buffers that tests name
+    READ_POOL7, READ_GTABLE, READ_POOL10, READ_CACHE_ENTS = 8, 9, 10, 11
+    GTABLE_ENTRIES, GTABLE_ENTRY_BYTES = 11 << 24, 64
+
+    def debug_read(self, which, offset, nbytes):
+        """lamd_debug_read: nbytes at offset of internal buffer `which` (include/lightning_amd_debug.h) as numpy uint8"""
+        out = np.zeros(max(1, nbytes), dtype=np.uint8)
+        self._chk(self._lib.lamd_debug_read(self._ctx, int(which), offset, nbytes, out.ctypes.data))
+        return out[:nbytes]
+
+    def gtable_audit(self, first, count, image=None):
+        """lamd_debug_gtable_audit over the entries [first, first + count) of the static G table; image: a torch uint8 / int32 device tensor of
+        exactly count * 64 bytes that replaces the range.  -> dict(bad, first_bad, first_reason, listed=[(index, reason), ...] (at most 64))"""
+        ptr = None
+        if image is not None:
+            if image.numel() * image.element_size() != count * self.GTABLE_ENTRY_BYTES or not image.is_contiguous():
+                raise ValueError("image must hold exactly count entries of 64 bytes")
+            import torch
+            torch.cuda.current_stream().synchronize()      # a diagnostic: the image is complete before the audit reads it
+            ptr = image.data_ptr()
+        r = _ffi.LamdGtableAuditResult()
+        self._chk(self._lib.lamd_debug_gtable_audit(self._ctx, first, count, ptr, ctypes.byref(r)))
+        return dict(bad=int(r.bad), first_bad=int(r.first_bad) if r.bad else None, first_reason=int(r.first_reason),
+                    listed=sorted((int(r.list_index[i]), int(r.list_reason[i])) for i in range(r.n_list)))
+
     def synchronize(self):
         self._chk(self._lib.lamd_synchronize(self._ctx))
 

@@ -92,6 +92,25 @@ void dm_gtable_entry(int w, u32 d, u8 *out64) {
   words_to_be(out64 + 32, yw);
 }
 
+// ---- the G-table audit (lightning_amd/csrc/table_audit.h; lamd_debug_gtable_audit runs the same function on the GPU)
+}  // extern "C"
+#include "../lightning_amd/csrc/table_audit.h"
+extern "C" {
+int dm_gtable_window_bits(void) { return GTABLE_WINDOW_BITS; }
+size_t dm_gtable_entries(void) { return GTABLE_ENTRIES; }
+int dm_gtable_entry_words(void) { return GT_ENTRY_WORDS; }
+// the harness's own table as stored (GTABLE_ENTRIES * GT_ENTRY_WORDS words)
+void dm_gtable_image(u32 *out) { dm_init(); memcpy(out, g_table.data(), g_table.size() * sizeof(u32)); }
+// reasons[k] = audit of entry first + k of `table` (NULL: the harness's own), the entries [first, first + count) read from `image` if given;
+// returns the number of bad entries
+size_t dm_gtable_audit(const u32 *table, size_t first, size_t count, const u32 *image, u32 *reasons) {
+  dm_init();
+  const gt_view v = {table ? table : g_table.data(), image, first, count};
+  size_t bad = 0;
+  for (size_t k = 0; k < count; k++) bad += (reasons[k] = gtable_audit_entry(v, first + k)) != 0;
+  return bad;
+}
+
 // Whole pipeline exactly as the kernels stage it.  threads = how many "prep threads" share the batch
 // (exercises the Montgomery batch inversion with different group sizes).
 void dm_ecdsa_verify_batch(size_t n, const u8 *hash32, const u8 *sig64, const u8 *pub, int publen, int pubstride, u8 *out, size_t threads) {

@@ -22,7 +22,7 @@ H = bytes.fromhex
 def dm():
     so = os.path.join(HERE, "libdevmath_host.so")
     srcs = [os.path.join(HERE, "devmath_host.cpp")] + [os.path.join(ROOT, "lightning_amd", "csrc", f)
-                                                       for f in ("lamd_common.h", "fe.h", "scalar.h", "group.h", "sha256.h", "verify_core.h", "fuzz.h")]
+                                                       for f in ("lamd_common.h", "fe.h", "scalar.h", "group.h", "sha256.h", "verify_core.h", "fuzz.h", "table_audit.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
     L = ctypes.CDLL(so)
@@ -444,16 +444,23 @@ def test_ladder_hot_form_special_scalars_and_its_table(dm):
     assert dm.dm_ladder_suspects(1) == 0
 
 
-def test_gtable_windows_that_straddle_words(kat):
-    """the shipped G table uses 24-bit windows (11 windows, the last one runs past bit 255, two of three straddle a 32-bit word);
-    the same digit extraction and table code built for the host with 11-bit windows must give the golden verdicts"""
+@pytest.fixture(scope="session")
+def dm_w11():
+    """the harness built with 11-bit G-table windows (24 windows: they straddle 32-bit words and the last one runs past bit 255)"""
     so = os.path.join(HERE, "libdevmath_host_w11.so")
     src = os.path.join(HERE, "devmath_host.cpp")
-    hdr = os.path.join(ROOT, "lightning_amd", "csrc", "verify_core.h")
-    if not os.path.exists(so) or max(os.path.getmtime(src), os.path.getmtime(hdr)) > os.path.getmtime(so):
+    hdrs = [os.path.join(ROOT, "lightning_amd", "csrc", f) for f in ("verify_core.h", "table_audit.h")]
+    if not os.path.exists(so) or max(os.path.getmtime(f) for f in [src] + hdrs) > os.path.getmtime(so):
         subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-DLAMD_GTABLE_WINDOW_BITS=11", "-DDM_NO_KEYED", "-o", so, src])
     L = ctypes.CDLL(so)
     L.dm_init()
+    return L
+
+
+def test_gtable_windows_that_straddle_words(kat, dm_w11):
+    """the shipped G table uses 24-bit windows (11 windows, the last one runs past bit 255, two of three straddle a 32-bit word);
+    the same digit extraction and table code built for the host with 11-bit windows must give the golden verdicts"""
+    L = dm_w11
     o = ctypes.create_string_buffer(64)
     for w, d in ((0, 1), (2, 2047), (5, 1000), (23, 7)):          # window 23 holds bits 253..263
         L.dm_gtable_entry(w, d, o)
@@ -472,6 +479,133 @@ def test_gtable_windows_that_straddle_words(kat):
                               b"".join(H(v["sig"]) for v in rows), out)
     bad = [v["name"] for v, g in zip(rows, out.raw) if bool(g) != v["expect"]]
     assert not bad, bad[:10]
+
+
+class _HostTable:
+    """the G table a harness built for itself and the audit function (table_audit.h) over it or over a corrupted copy"""
+
+    def __init__(self, L):
+        L.dm_gtable_entries.restype = ctypes.c_size_t
+        L.dm_gtable_audit.restype = ctypes.c_size_t
+        self.L, self.bits, self.n = L, L.dm_gtable_window_bits(), L.dm_gtable_entries()
+        assert L.dm_gtable_entry_words() == 16
+        self.nwin = self.n >> self.bits
+        self.img = np.zeros((self.n, 16), dtype=np.uint32)
+        L.dm_gtable_image(ctypes.c_void_p(self.img.ctypes.data))
+        self.img.setflags(write=False)
+
+    def audit(self, table=None, first=0, count=None, image=None):
+        count = self.n - first if count is None else count
+        reasons = np.zeros(max(1, count), dtype=np.uint32)
+        for a in (table, image):
+            assert a is None or (a.dtype == np.uint32 and a.flags.c_contiguous)
+        assert image is None or len(image) == count
+        bad = self.L.dm_gtable_audit(ctypes.c_void_p(table.ctypes.data if table is not None else None), ctypes.c_size_t(first), ctypes.c_size_t(count),
+                                     ctypes.c_void_p(image.ctypes.data if image is not None else None), ctypes.c_void_p(reasons.ctypes.data))
+        assert bad == np.count_nonzero(reasons[:count])
+        return reasons[:count]
+
+    def src(self, idx):
+        return self.img[idx].copy()
+
+
+@pytest.fixture(scope="session", params=["w8", "w11"])
+def gt_host(request):
+    return _HostTable(request.getfixturevalue("dm" if request.param == "w8" else "dm_w11"))
+
+
+def test_gtable_audit_clean_table_is_the_closed_form(gt_host, orc):
+    """the whole host-built table audits clean, and it IS d * 2^(BITS*w) * G entry for entry (C oracle): what a clean audit claims"""
+    import gtable_cases as gc
+    t = gt_host
+    assert not t.audit().any()
+    for idx in range(t.n):
+        w, d = idx >> t.bits, idx & ((1 << t.bits) - 1)
+        if d == 0:
+            assert not t.img[idx].any()
+            continue
+        pt = orc.pubkey_create(((d << (t.bits * w)) % N).to_bytes(32, "big"))
+        assert gc.xy(t.img[idx]) == (int.from_bytes(pt[1:33], "big"), int.from_bytes(pt[33:], "big")), (w, d)
+
+
+def test_gtable_audit_flags_exactly_what_the_relations_predict(gt_host):
+    """every corruption class, at digits 2 and 3 (the tangent rule and the first chord), in the middle of a window, at its last digits, in the first,
+    a middle and the last window: the bad set is the corrupted entry and whatever reads it, nothing else; the reason mask names the fault"""
+    import gtable_cases as gc
+    t = gt_host
+    last = (1 << t.bits) - 1
+    for w in (0, 1, t.nwin // 2, t.nwin - 1):
+        lo, hi = w << t.bits, min(t.n, (w + 2) << t.bits)                  # everything that reads window w lies in it or in the next one
+        for d in (2, 3, 4, 64, last // 2, last - 3, last - 2):
+            i = (w << t.bits) | d
+            for f in gc.GENERIC:
+                img = t.img.copy()
+                corrupted, must, must_not = f(img, 0, i, t.src)
+                gc.check(t.audit(table=img, first=lo, count=hi - lo), lo, hi - lo, corrupted, t.bits, t.nwin, i, must, must_not, f.__name__)
+        # the last two digits cannot take the classes that read d + 1 / d + 2 from the same window
+        for d in (last - 1, last):
+            i = (w << t.bits) | d
+            for f in (gc.flip_x_bit, gc.flip_y_bit, gc.negate_y, gc.noncanonical_x, gc.noncanonical_y, gc.all_zero):
+                img = t.img.copy()
+                corrupted, must, must_not = f(img, 0, i, t.src)
+                gc.check(t.audit(table=img, first=lo, count=hi - lo), lo, hi - lo, corrupted, t.bits, t.nwin, i, must, must_not, f.__name__)
+        assert not t.audit(table=img, count=lo).any() and not t.audit(table=img, first=hi).any()      # ... and the rest of the table, once per window
+        img = t.img.copy()
+        i = w << t.bits
+        corrupted, must, must_not = gc.nonzero_digit0(img, 0, i, t.src)
+        r = t.audit(table=img)
+        gc.check(r, 0, t.n, corrupted, t.bits, t.nwin, i, must, must_not, "nonzero_digit0")
+        assert np.count_nonzero(r) == 1
+
+
+def test_gtable_audit_wrong_base_entries(gt_host):
+    """a wrong entry 1 fails through its whole window and through entry 1 of the next one (whose rule reads it as B'), and nowhere else"""
+    import gtable_cases as gc
+    t = gt_host
+    last = (1 << t.bits) - 1
+    two_g = pyref.pmul(2, pyref.G)
+    img = t.img.copy()
+    img[1] = gc.entry(*two_g)                                              # entry 1 of window 0 := 2G
+    r = t.audit(table=img)
+    assert {int(k) for k in np.nonzero(r)[0]} == set(range(1, last + 1)) | {(1 << t.bits) | 1}
+    assert int(r[1]) == gc.ANCHOR                                          # a curve point, canonical: only the anchor knows
+    assert int(r[3]) & gc.DEGENERATE                                       # 3: P1 = 2B coincides with the "base"
+    for w in (1, t.nwin // 2, t.nwin - 1):
+        b = (w << t.bits) | 1
+        for f in (lambda im: im.__setitem__(b, t.img[b + 4]),             # another point of the table (5B)
+                  lambda im: im.__setitem__(b, gc.entry(*gc.small_x_point())),    # a foreign curve point
+                  lambda im: gc.negate_y(im, 0, b, t.src),
+                  lambda im: gc.flip_x_bit(im, 0, b, t.src)):
+            img = t.img.copy()
+            f(img)
+            r = t.audit(table=img)
+            want = set(range(b, b + last)) | ({((w + 1) << t.bits) | 1} if w + 1 < t.nwin else set())
+            assert {int(k) for k in np.nonzero(r)[0]} == want == gc.affected({b}, t.bits, t.nwin), w
+            assert int(r[b]) & (gc.X | gc.Y | gc.OFF_CURVE) and not int(r[b]) & (gc.ANCHOR | gc.ZERO | gc.NONCANON)
+
+
+def test_gtable_audit_replacement_image_is_confined_to_its_range(gt_host):
+    """the audit of a range with a replacement image reads the range from the image and everything else (the base entry, the predecessor of the
+    first entry, the previous window) from the table: the form the device tests use for their negative controls"""
+    import gtable_cases as gc
+    t = gt_host
+    last = (1 << t.bits) - 1
+    w = t.nwin // 2
+    first, count = (w << t.bits) + last - 40, 41                           # ends at the window's last entry
+    img = t.img[first:first + count].copy()
+    assert not t.audit(first=first, count=count, image=img).any()
+    assert not t.audit(first=first, count=0, image=None).any()
+    i = first + count - 1
+    gc.flip_y_bit(img, first, i, t.src)
+    r = t.audit(first=first, count=count, image=img)
+    assert {first + int(k) for k in np.nonzero(r)[0]} == {i}
+    nxt = ((w + 1) << t.bits) | 1                                          # reads the window's last entry -- from the TABLE: clean
+    assert not t.audit(first=nxt, count=1).any()
+    # a range that holds only a corrupted entry's successor sees the clean table behind it; one that holds both sees both
+    img2 = t.img[first:first + 2].copy()
+    gc.negate_y(img2, first, first, t.src)
+    assert list(t.audit(first=first, count=2, image=img2)) == [gc.Y, gc.X | gc.Y]
+    assert not t.audit(first=first + 1, count=1, image=np.ascontiguousarray(img2[1:])).any()
 
 
 def _recover_cases(orc, rnd, n):
