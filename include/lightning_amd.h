@@ -261,6 +261,51 @@ int lamd_bolt11_check_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const 
 enum { LAMD_MSG_OK = 0, LAMD_MSG_BAD_ZBASE = -1, LAMD_MSG_BAD_LENGTH = -2, LAMD_MSG_BAD_SIG = -3, LAMD_MSG_NO_KEY = -4 };
 int lamd_checkmessage_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *moff,
 			    const uint8_t *zbase, const uint64_t *zoff, int8_t *status, uint8_t *node_id33);
+/* lamd_bolt12_check_text_batch: BOLT #12 offers, invoice requests and invoices FROM THEIR TEXT -- the stage in front of
+ * lamd_bolt12_check_signature_batch, built like lamd_bolt11_check_batch: the front-end kernel (k_bolt12_text_front: the `+` joins, bech32 without
+ * checksum, the TLV walk, the two ids, merkle_tlv() and sighash_from_merkle()), the key-parse kernel, the BIP-340 batch over all n rows and the
+ * merge are queued on one stream without the host waiting in between.  String i = strs[off[i] .. off[i+1]) (off: n+1 entries), no terminator, no
+ * length cap: exactly what offer_decode(), invrequest_decode() or invoice_decode() would be handed; a batch may mix the three kinds.
+ * status[i] is the FIRST of these that applies, in the reference's order:
+ *   -1 LAMD_B12_UNFINISHED     b12_string_to_data (common/bolt12.c:125-142): a '+' that is neither the first nor the last byte and does not directly
+ *                              follow another joining '+' is dropped, and so are the bytes ccan's cisspace accepts (space, \t \n \v \f \r) behind
+ *                              it; the string ends while still inside such a join
+ *   -2 LAMD_B12_BAD_BECH32     from_bech32_charset + bech32_pull_bits (common/bech32_util.c:34-120) over the collapsed string: no '1' (the
+ *                              separator is the FIRST '1'; an empty hrp passes here); a data byte >= 128 or outside the alphabet after case
+ *                              folding; both an upper-case and a lower-case letter anywhere in hrp or data; 5*count mod 8 >= 5; a non-zero
+ *                              padding bit.  The reference keeps the hrp as a C string: a NUL byte in it ends it, for the case test too
+ *   -3 LAMD_B12_BAD_PREFIX     the lower-cased hrp is not "lno", "lnr" or "lni"
+ *   -4 LAMD_B12_MALFORMED      the decoded bytes break fromwire_tlv's generic rules (wire/tlvstream.c:144-300: type and length minimal BigSize, the
+ *                              length inside the stream, types strictly increasing); or, for an invoice request / an invoice, the kind's key field
+ *                              (88 invreq_payer_id / 176 invoice_node_id) is present with a length other than 33 or its bytes are no valid
+ *                              compressed key (fromwire_pubkey, bitcoin/pubkey.c:102-113), or field 240 is present with a length other than 64
+ *   -5 LAMD_B12_OUT_OF_RANGE   any_field_outside_range (common/bolt12.c:211-213, :362-364).  Offer: any field outside 1..79 and
+ *                              1000000000..1999999999.  Invoice request: any field other than types 240..1000 outside 0..159 and
+ *                              1000000000..2999999999.  Invoices have no such rule
+ *   -6 LAMD_B12_NO_KEY         an invoice request or invoice without its key field ("Missing invreq_payer_id" / "Missing node_id")
+ *   -7 LAMD_B12_NO_SIGNATURE   an invoice request or invoice without field 240
+ *   -8 LAMD_B12_BAD_SIGNATURE  bolt12_check_signature(fields, "invoice_request" | "invoice", "signature", key, sig) fails (common/bolt12.c:80-110,
+ *                              plugins/offers_invreq_hook.c:1064-1077)
+ *    0 LAMD_B12_OK             an offer that reached here carries no signature to check
+ * kind[i] = LAMD_B12_KIND_*: set from the prefix test on, NONE for statuses -1 .. -3.  signer33 + 33*i = the key field's 33 bytes for OK rows of
+ * kind invreq / invoice, zero otherwise.  sighash32 + 32*i (may be NULL) = sighash_from_merkle() for rows of kind invreq / invoice whose status is
+ * OK or BAD_SIGNATURE, zero otherwise.  offer_id32 + 32*i (may be NULL) = calc_offer() for OK rows: SHA-256 over tlv_span(1, 79) ||
+ * tlv_span(1000000000, 1999999999) of the decoded bytes; zero otherwise.  invreq_id32 + 32*i (may be NULL) = calc_invreq() for OK rows of kind
+ * invreq / invoice: the spans are 0..159 and 1000000000..2999999999; zero otherwise.  tlv_span is the reference's (common/bolt12.c:670-695) with one
+ * deviation: where it would subtract from a null pointer (the first field at or above the lower bound lies above the upper bound and no field
+ * precedes it) the span is empty.  An id over two empty spans is SHA-256 of nothing (e3b0c442...).
+ * CONTRACT: only the kind's key field and field 240 are interpreted.  The unknown-even-type rule (it needs each message's list of known types), the
+ * inner encodings of all other known fields, features, chains, required fields, paths and expiry stay with the host's decoder.  For a string the
+ * reference accepts the status is OK and the key is its signer; for a string it rejects for one of the reasons above, with nothing unchecked
+ * failing earlier, the status is that reason.
+ * n == 0 is LAMD_OK; a NULL strs, off, status, kind or signer33, and decreasing offsets, are LAMD_ERR_ARG; calls of more than the chunk size run
+ * their curve work chunk by chunk; with lamd_set_timing(ctx, 1) lamd_info.last_text_ms covers this call's launches too. */
+enum { LAMD_B12_OK = 0, LAMD_B12_UNFINISHED = -1, LAMD_B12_BAD_BECH32 = -2, LAMD_B12_BAD_PREFIX = -3, LAMD_B12_MALFORMED = -4,
+       LAMD_B12_OUT_OF_RANGE = -5, LAMD_B12_NO_KEY = -6, LAMD_B12_NO_SIGNATURE = -7, LAMD_B12_BAD_SIGNATURE = -8 };
+enum { LAMD_B12_KIND_NONE = 0, LAMD_B12_KIND_OFFER = 1, LAMD_B12_KIND_INVREQ = 2, LAMD_B12_KIND_INVOICE = 3 };
+int lamd_bolt12_check_text_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, int8_t *status, uint8_t *kind,
+				 uint8_t *signer33, uint8_t *sighash32 /* may be NULL */, uint8_t *offer_id32 /* may be NULL */,
+				 uint8_t *invreq_id32 /* may be NULL */);
 
 /* grind_htlc_tx_fee() (onchaind/onchaind.c:388-438): find the feerate whose fee makes `sig64` (one remote HTLC signature,
  * one key) verify.  For feerate = min_feerate..max_feerate: fee = feerate * weight / 1000 (amount_tx_fee), equal consecutive
@@ -598,7 +643,7 @@ typedef struct {
 	int hw_queues_env;        /* GPU_MAX_HW_QUEUES as lamd_init() found it (0 = unset: the runtime's default of 4; < 16 costs overlap between the lanes) */
 	int queue_sets;           /* staging sets of the streaming queue = the most flushes that may be outstanding */
 	size_t last_flush_inplace_rows; /* rows the last lamd_flush() sent to the device straight from the callers' registered memory (queued in place, not copied) */
-	double last_text_ms[2];   /* with timing on: device time of the last lamd_bolt11_check_batch / lamd_checkmessage_batch -- the front-end kernel; key parse, curve work and merge */
+	double last_text_ms[2];   /* with timing on: device time of the last lamd_bolt11_check_batch / lamd_checkmessage_batch / lamd_bolt12_check_text_batch --the front-end kernel; key parse, curve work and merge */
 } lamd_info;
 int lamd_get_info(lamd_ctx *ctx, lamd_info *info);
 int lamd_get_lane_info(lamd_ctx *ctx, int lane, lamd_info *info); /* the last call that ran on lane 0 .. lanes-1 */

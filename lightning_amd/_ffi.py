@@ -83,6 +83,7 @@ SYMBOLS = {
     "lamd_ecdsa_recover_batch_device": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
     "lamd_bolt11_check_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
     "lamd_checkmessage_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
+    "lamd_bolt12_check_text_batch": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]),
     "lamd_grind_htlc_tx_fee": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_sz, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                               ctypes.c_uint32, c_u8p, ctypes.c_uint8, ctypes.c_int, c_u8p, ctypes.POINTER(ctypes.c_uint32),
                                               ctypes.POINTER(ctypes.c_uint64)]),

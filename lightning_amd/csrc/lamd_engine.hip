@@ -26,6 +26,7 @@
 #include "store_latest.h"
 #include "bolt11.h"
 #include "table_audit.h"
+#include "bolt12_text.h"
 
 using namespace lamd;
 
@@ -471,6 +472,50 @@ __global__ void __launch_bounds__(256) k_text_merge(size_t n, const int8_t *__re
   status[i] = (int8_t)st;
   const u8 *src = hn ? key33 + 33 * i : pub_rec + 33 * i;
   for (int b = 0; b < 33; b++) node_id33[33 * i + b] = st == 0 ? src[b] : 0;
+}
+
+// ---- BOLT #12 from its text, one string per lane (bolt12_text.h).  Row i decodes into scratch[off[i] .. off[i+1]): a string never decodes to more bytes
+// than it has, so the rows cannot overlap.  Only a row with status 0 so far and a key of its own (an invoice request, an invoice) belongs to the BIP-340
+// batch; every other row gets what the batch's early reject removes -- a zero signature under the generator's x -- so the batch runs over all n rows.
+// key33 keeps a present key whatever the status behind it (-5, -7, 0), for the key-parse kernel's validity byte; without one it holds the generator.
+__global__ void __launch_bounds__(64) k_bolt12_text_front(size_t n, const u8 *__restrict__ strs, const u64 *__restrict__ off, u8 *__restrict__ scratch,
+                                                          bolt12_text_mids mids, int8_t *__restrict__ pre, u8 *__restrict__ kind, u8 *__restrict__ have_key,
+                                                          u8 *__restrict__ key33, u8 *__restrict__ xonly, u8 *__restrict__ sig64, u8 *__restrict__ hash32,
+                                                          u8 *__restrict__ offer_id, u8 *__restrict__ invreq_id) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t len = (size_t)(off[i + 1] - off[i]);
+  size_t dlen;
+  u8 kd, hk;
+  const int st = bolt12_text_front_one(strs + off[i], len, scratch + off[i], len, &dlen, mids, &kd, key33 + 33 * i, &hk, sig64 + 64 * i, hash32 + 32 * i,
+                                       offer_id + 32 * i, invreq_id + 32 * i);
+  pre[i] = (int8_t)st;
+  kind[i] = kd;
+  have_key[i] = hk;
+  const bool ver = st == LAMD_B12_OK && kd != LAMD_B12_KIND_OFFER;
+  for (int b = 0; b < 32; b++) xonly[32 * i + b] = ver ? key33[33 * i + 1 + b] : TEXT_DUMMY_KEY[1 + b];
+  if (!hk)
+    for (int b = 0; b < 33; b++) key33[33 * i + b] = TEXT_DUMMY_KEY[b];
+}
+// status, signer and ids of a row from what the stages left.  A present key that is no curve point is MALFORMED (fromwire_pubkey fails inside
+// fromwire_tlv), ahead of what the ranges, field 240 and the signature say, and takes the row's hash with it.
+__global__ void __launch_bounds__(256) k_bolt12_text_merge(size_t n, const int8_t *__restrict__ pre, const u8 *__restrict__ kind, const u8 *__restrict__ have_key,
+                                                           const u8 *__restrict__ keyok, const u8 *__restrict__ ok_ver, const u8 *__restrict__ key33,
+                                                           u8 *__restrict__ hash32, u8 *__restrict__ offer_id, u8 *__restrict__ invreq_id,
+                                                           int8_t *__restrict__ status, u8 *__restrict__ signer33) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int st = pre[i];
+  const bool own_key = kind[i] == LAMD_B12_KIND_INVREQ || kind[i] == LAMD_B12_KIND_INVOICE;
+  if (have_key[i] && !keyok[i] && (st == LAMD_B12_OK || st == LAMD_B12_OUT_OF_RANGE || st == LAMD_B12_NO_SIGNATURE)) {
+    st = LAMD_B12_MALFORMED;
+    for (int b = 0; b < 32; b++) hash32[32 * i + b] = 0;
+  }
+  if (st == LAMD_B12_OK && own_key) st = ok_ver[i] == 1 ? LAMD_B12_OK : LAMD_B12_BAD_SIGNATURE;
+  status[i] = (int8_t)st;
+  if (st != LAMD_B12_OK)
+    for (int b = 0; b < 32; b++) offer_id[32 * i + b] = invreq_id[32 * i + b] = 0;
+  for (int b = 0; b < 33; b++) signer33[33 * i + b] = st == LAMD_B12_OK && own_key ? key33[33 * i + b] : 0;
 }
 
 // ---- fee grind (verify_core.h "fee grind"): one thread prepares, one thread per candidate feerate
@@ -3923,6 +3968,78 @@ extern "C" int lamd_checkmessage_batch(lamd_ctx *ctx, size_t n, const uint8_t *m
   if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
   hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(node_id33, c.node_id, n * 33, hipMemcpyDeviceToHost, ctx->stream);
+  if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
+  if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
+  return text_timing_end(ctx);
+}
+
+// ---- BOLT #12 offers, invoice requests and invoices from their text (bolt12_text.h): lamd_bolt11_check_batch step for step, with the BIP-340 batch in
+// place of the ECDSA and recovery batches.  The decode scratch lies behind the strings in the same buffer.
+struct b12_cols {
+  int8_t *pre, *status;
+  u8 *hash, *offer_id, *invreq_id, *sig, *xonly, *key, *signer, *kind, *have_key, *keyok, *ok_ver;
+  u32 *qwords;
+};
+static size_t b12_cols_bytes(size_t n) { return n * (64 + 4 * 32 + 64 + 33 + 33 + 6) + 64; }
+static b12_cols b12_cols_at(u8 *p, size_t n) {
+  b12_cols c;
+  c.qwords = (u32 *)p; p += 64 * n;     // what k_keys writes next to keyok (16-byte aligned: uint4 stores); never read
+  c.hash = p; p += 32 * n;
+  c.xonly = p; p += 32 * n;
+  c.sig = p; p += 64 * n;
+  c.offer_id = p; p += 32 * n;
+  c.invreq_id = p; p += 32 * n;
+  c.key = p; p += 33 * n;
+  c.signer = p; p += 33 * n;
+  c.pre = (int8_t *)p; p += n;
+  c.status = (int8_t *)p; p += n;
+  c.kind = p; p += n;
+  c.have_key = p; p += n;
+  c.keyok = p; p += n;
+  c.ok_ver = p;
+  return c;
+}
+extern "C" int lamd_bolt12_check_text_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, int8_t *status, uint8_t *kind,
+                                            uint8_t *signer33, uint8_t *sighash32, uint8_t *offer_id32, uint8_t *invreq_id32) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (n == 0) return LAMD_OK;
+  if (!strs || !off || !status || !kind || !signer33) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
+  if (off[n] < off[0]) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
+  const size_t total = (size_t)(off[n] - off[0]);
+  if ((rc = ensure(ctx, &ctx->g_msgs, 2 * total + 64)) != LAMD_OK) return rc;   // strings | decode scratch
+  if ((rc = ensure(ctx, &ctx->g_off, (n + 1) * 8)) != LAMD_OK) return rc;
+  if ((rc = ensure(ctx, &ctx->tx_cols, b12_cols_bytes(n))) != LAMD_OK) return rc;
+  const b12_cols c = b12_cols_at(ctx->tx_cols.as<u8>(), n);
+  bolt12_text_mids mids;
+  bolt12_text_make_mids(&mids);
+  std::vector<u64> rel;   // the queued copy reads it: lives until the stream has been synchronised
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return code;
+  };
+  if ((rc = text_upload(ctx, n, strs, off, &ctx->g_msgs, 0, ctx->g_off.as<u64>(), rel)) != LAMD_OK) return fail(rc);
+  if ((rc = text_timing_begin(ctx)) != LAMD_OK) return fail(rc);
+  hipLaunchKernelGGL(k_bolt12_text_front, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(),
+                     ctx->g_msgs.as<u8>() + total, mids, c.pre, c.kind, c.have_key, c.key, c.xonly, c.sig, c.hash, c.offer_id, c.invreq_id);
+  if (ctx->timing && hipEventRecord(ctx->ev_text[1], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
+  // the key-parse kernel for its validity byte alone, as in lamd_bolt11_check_batch: a bad key counts whatever the signature bytes are
+  hipLaunchKernelGGL(k_keys, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const u8 *)c.key, 33, (size_t)33, (const u32 *)nullptr, c.qwords, c.keyok,
+                     (const u32 *)nullptr);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return fail(LAMD_ERR_HIP); }
+  if ((rc = run_device(ctx, MODE_SCHNORR, n, c.hash, c.sig, c.xonly, 32, 32, c.ok_ver)) != LAMD_OK) return fail(rc);
+  hipLaunchKernelGGL(k_bolt12_text_merge, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const int8_t *)c.pre, (const u8 *)c.kind, (const u8 *)c.have_key,
+                     (const u8 *)c.keyok, (const u8 *)c.ok_ver, (const u8 *)c.key, c.hash, c.offer_id, c.invreq_id, c.status, c.signer);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text merge: launch failed"; return fail(LAMD_ERR_HIP); }
+  if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
+  hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(kind, c.kind, n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(signer33, c.signer, n * 33, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && sighash32) e = hipMemcpyAsync(sighash32, c.hash, n * 32, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && offer_id32) e = hipMemcpyAsync(offer_id32, c.offer_id, n * 32, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && invreq_id32) e = hipMemcpyAsync(invreq_id32, c.invreq_id, n * 32, hipMemcpyDeviceToHost, ctx->stream);
   if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
   if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
   return text_timing_end(ctx);

@@ -286,6 +286,19 @@ class Engine:
                                                     node.ctypes.data))
         return status, node
 
+    def bolt12_check(self, strings):
+        """strings: BOLT #12 offers, invoice requests and invoices as offer_decode() / invrequest_decode() / invoice_decode() take them (str or
+        bytes; the kinds may be mixed) -> (status int8 [n] (LAMD_B12_*), kind uint8 [n] (LAMD_B12_KIND_*), signer uint8 [n,33], sighash uint8
+        [n,32], offer_id uint8 [n,32], invreq_id uint8 [n,32]): join collapse, bech32 decoding, the TLV walk, the ids, the merkle root and the
+        BIP-340 verification under the string's own key on the device (lamd_bolt12_check_text_batch)"""
+        blob, off = self._streams([x.encode("latin-1") if isinstance(x, str) else x for x in strings])
+        n = len(strings)
+        status, kind, signer = np.zeros(n, dtype=np.int8), np.zeros(n, dtype=np.uint8), np.zeros((n, 33), dtype=np.uint8)
+        sighash, offer_id, invreq_id = (np.zeros((n, 32), dtype=np.uint8) for _ in range(3))
+        self._chk(self._lib.lamd_bolt12_check_text_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, status.ctypes.data, kind.ctypes.data,
+                                                         signer.ctypes.data, sighash.ctypes.data, offer_id.ctypes.data, invreq_id.ctypes.data))
+        return status, kind, signer, sighash, offer_id, invreq_id
+
     def _after_torch(self):
         """order the next submission after what torch's current stream holds (the tensors handed to the *_device methods are
         usually produced there); a device-side event, no host synchronisation.  The caller still has to keep the tensors alive
