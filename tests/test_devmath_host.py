@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import chosen_scalars as cs
 import pyref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -364,13 +365,10 @@ def test_task_split_of_the_latency_path_gives_the_golden_verdicts(dm, kat):
 def test_keyed_ecmult_special_scalars(dm):
     """u1*G + u2*Q through the comb for scalars that stress the recoding: zero / even / tiny GLV halves, halves that cancel,
     u2 = +-lambda^i (one half exactly +-1), the partial sums that meet -u1*G, and seeded random ones"""
-    LAM = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
     d = 0x6C1F00D5A3E2B4C7918D7E6F5A4B3C2D1E0F99887766554433221100FFEEDDCC
     Q = pyref.pubkey_create(d)
     rng = random.Random(77)
-    u2s = [0, 1, 2, 3, 4, N - 1, N - 2, LAM, N - LAM, LAM + 1, LAM - 1, 2 * LAM % N, (LAM + 2) % N, LAM * LAM % N, (N - LAM * LAM) % N,
-           1 << 127, (1 << 128) - 1, 1 << 128, (1 << 128) + 1, ((1 << 127) * LAM + 2) % N, (N + 1) // 2]
-    u2s += [rng.randrange(N) for _ in range(12)]
+    u2s = [0] + cs.U2_COMB + [rng.randrange(N) for _ in range(12)]
     o = ctypes.create_string_buffer(64)
     dm.dm_suspects.restype = ctypes.c_size_t
     for T in (7, 10):
@@ -401,7 +399,6 @@ def test_ladder_hot_form_special_scalars_and_its_table(dm):
     """the per-signature ladder in its hot form (ecmult_lane_fast: both halves odd, signed odd 4-bit digits, the table 1Q, 3Q .. 15Q, bare
     additions, one Z == 0 test) against the complete ladder and the model: the table's entries are (2e+1)Q on the curve its Z names; scalars that
     stress the recoding (zero / even / tiny halves, halves that cancel, +-lambda^i, every small u2, partial sums that meet -u1*G) and random ones"""
-    LAM = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
     BETA = 0x7AE96A2B657C07106E64479EAC3434E99CF0497512F58995C1396C28719501EE
     rng = random.Random(1515)
     dm.dm_ladder_suspects.restype = ctypes.c_size_t
@@ -418,10 +415,7 @@ def test_ladder_hot_form_special_scalars_and_its_table(dm):
             assert bx == x * BETA % P
     d = 0x6C1F00D5A3E2B4C7918D7E6F5A4B3C2D1E0F99887766554433221100FFEEDDCC
     Q = pyref.pubkey_create(d)
-    u2s = list(range(0, 40)) + [N - 1, N - 2, N - 3, LAM, N - LAM, LAM + 1, LAM - 1, 2 * LAM % N, (LAM + 2) % N, 3 * LAM % N, (15 * LAM) % N, (16 * LAM + 1) % N,
-                                LAM * LAM % N, (N - LAM * LAM) % N, 1 << 127, (1 << 128) - 1, 1 << 128, (1 << 128) + 1, ((1 << 127) * LAM + 2) % N, (N + 1) // 2,
-                                (1 << 129) - 1, ((1 << 128) - 1) * LAM % N, (0x88888888888888888888888888888888 * (LAM + 1)) % N]
-    u2s += [rng.randrange(N) for _ in range(40)]
+    u2s = cs.U2_LADDER + [rng.randrange(N) for _ in range(40)]
     o = ctypes.create_string_buffer(64)
     dm.dm_ladder_suspects(1)
     ninf = 0

@@ -8,11 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+import chosen_scalars as cs
 import pyref
 
 pytestmark = pytest.mark.gpu
 N = pyref.N
-LAM = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
 KEYS = (0x1F2E3D4C5B6A79881726354453627180AABBCCDDEEFF00112233445566778899, 0x6C1F00D5A3E2B4C7918D7E6F5A4B3C2D1E0F99887766554433221100FFEEDDCC)
 
 
@@ -129,9 +129,7 @@ def test_chosen_scalars_through_the_comb(eng_keyed, orc):
     e = eng_keyed
     d = KEYS[1]
     rng = random.Random(77)
-    u2s = [1, 2, 3, 4, N - 1, N - 2, LAM, N - LAM, LAM + 1, LAM - 1, 2 * LAM % N, (LAM + 2) % N, LAM * LAM % N, (N - LAM * LAM) % N,
-           1 << 127, (1 << 128) - 1, 1 << 128, (1 << 128) + 1, ((1 << 127) * LAM + 2) % N, (N + 1) // 2]      # (u2 = 0 is r = 0: not a signature)
-    u2s += [rng.randrange(1, N) for _ in range(12)]
+    u2s = cs.U2_COMB + [rng.randrange(1, N) for _ in range(12)]                                                # (u2 = 0 is r = 0: not a signature)
     pub = orc.pubkey_create(d.to_bytes(32, "big"))
     hs, sg, ninf = [], [], 0
     for u2 in u2s:
@@ -148,4 +146,31 @@ def test_chosen_scalars_through_the_comb(eng_keyed, orc):
     assert np.array_equal(got, exp), np.nonzero(got != exp)[0][:10]
     inf = e.info()
     assert inf["last_keyed"] == e.teeth and inf["last_hot_rows"] == len(hs) and inf["last_suspect_rows"] >= ninf == len(u2s), inf
+    assert np.array_equal(e.verify_ecdsa(*cols), exp)       # > 64 rows from host memory: the same path
+
+
+def test_chosen_scalars_through_the_comb_accepting(eng_keyed, orc):
+    """the same u2 list on rows that ACCEPT iff the comb computes exactly u1*G + u2*Q (chosen_scalars.py: r = x(R), s = r/u2, hash = u1*s under the two
+    keys above; u1 random, redrawn until s is low, and u1 = 0, 1 where one of the keys gives a low s), each with its near-miss twin (one digit of
+    the G walk off by one: rejects), next to the rows whose sum is infinity: a comb that computes a wrong point at u2 = lambda + 1 fails here, where
+    the test above -- every expected verdict False -- would not notice.  The suspect counter and the infinity rows are checked as above."""
+    e = eng_keyed
+    rng = random.Random(78)
+    u2s = cs.U2_COMB + [rng.randrange(1, N) for _ in range(12)]
+    pairs = [("u2:%d" % j, None, u2) for j, u2 in enumerate(u2s)] + [("u1=%d:%d" % (u1, j), u1, u2) for u1 in (0, 1) for j, u2 in enumerate(u2s)]
+    acc, unreachable = cs.verify_rows_fixed_keys(orc, rng, pairs, list(KEYS))
+    assert sum(r.tag.startswith("u2:") for r in acc) == len(u2s) and all(r.exact() for r in acc)      # every u2 of the list is hit exactly
+    assert len(acc) + len(unreachable) == len(pairs) and len(unreachable) < len(u2s)                  # (two keys: a pair is out of reach once in four)
+    rows = cs.with_twins(acc, 24)
+    pub = orc.pubkey_create(KEYS[1].to_bytes(32, "big"))
+    for u2 in u2s:                                           # s = 1, r = u2, hash = u1 = -u2*d: the sum is infinity
+        rows.append(cs.Row("verify", ((-u2 * KEYS[1]) % N).to_bytes(32, "big"), u2.to_bytes(32, "big") + (1).to_bytes(32, "big"), pub, (None, u2), "inf", expect=False))
+    cols = cs.columns(rows, 65)
+    exp = orc.ecdsa_verify_batch(cols[0], cols[1], cols[2], 65, 2).astype(bool)
+    assert np.array_equal(exp, np.array([r.expect for r in rows], dtype=bool)) and 0 < exp.sum() == len(acc)
+    e.cache_clear()
+    got = _on_device(e, "ecdsa", cols)
+    assert np.array_equal(got, exp), [(rows[i].tag, hex(rows[i].u1), hex(rows[i].u2)) for i in np.nonzero(got != exp)[0][:10]]
+    inf = e.info()
+    assert inf["last_keyed"] == e.teeth and inf["last_hot_rows"] == len(rows) and inf["last_suspect_rows"] >= len(u2s), inf
     assert np.array_equal(e.verify_ecdsa(*cols), exp)       # > 64 rows from host memory: the same path
