@@ -536,6 +536,90 @@ int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *store, size_t 
 				    uint8_t *reason, size_t *n_records, uint8_t *out, void *d_out, size_t out_cap,
 				    lamd_store_summary *summary, lamd_store_latest_summary *latest);
 
+/* ---- serving a trusted store: the channel digest of a gossip_store image on the device, and the replies to query_channel_range from it.
+ * What connectd/queries.c does per query -- gather_range() (:564-634) walks every channel, re-reads both channel_updates of each channel in
+ * range and checksums them, queue_channel_ranges() (:641-711) cuts the result into reply_channel_range messages -- split in two: the digest
+ * is built once per store, a batch of queries is answered from it.
+ *
+ * THE DIGEST.  store / len / d_store: the image, as in the audit, but either may be NULL (host `store` is copied, a resident d_store is read
+ * in place: e.g. the d_out a repair has left).  rec_off[n]: the records, from lamd_gossip_store_frame or, for a repair's output, the kept
+ * new_off in order.  verdict[n]: optional, the audit's.  The device reads headers and types itself; every read stays inside the image
+ * whatever rec_off holds.  The rules are gossmap's load (common/gossmap.c:451-509, :585-610); as in the audit, flags alone decide whether
+ * a record is live and tombstones are not applied.
+ *   COUNTS   record i counts iff its DELETED flag is clear and, with verdict, verdict[i] == LAMD_STORE_OK
+ *   CHANNEL  the lowest-index counting 256 of its scid; later 256 records of that scid are ignored
+ *   SLOT [a][d]  the HIGHEST-index counting 258 of >= 112 bytes whose scid (message offset 98) is that of channel a, with a < i, and
+ *            whose channel_flags & 1 (offset 111) is d: last in file order wins whatever the timestamps (update_channel(), not the
+ *            receive path).  A 258 shorter than 112 bytes is ignored -- deliberately: the reference would read past its end.
+ *   ENTRY    one per channel with at least one slot set (the policy of queries.c:603-607): scid; ts[d] = the be32 at message offset 106 of
+ *            the slot's record, or 0; csum[d] = crc32c(crc32c(0, m + 66, 40), m + 110, len - 110), or 0 (crc32_of_update, :429-470);
+ *            rec[3] = the record indices of the announcement and of the two updates, UINT32_MAX where there is none
+ * The entries are SORTED ASCENDING BY SCID.  That is the one deliberate difference from the reference, which since it dropped its uintmap
+ * emits channels in gossmap index order (:593-596) although BOLT #7 requires ascending short_channel_ids and its own split at block
+ * boundaries assumes them: tests/golden/gossip_store_mesh_3x3.bin, written by the reference, holds its channels out of order.
+ * Launches, one stream, no host wait between them: k_digest_index (scid index), k_digest_slots (a 32-bit atomicMax of index + 1 per
+ * slot), k_digest_chan (channels and compaction of (scid, announcement) pairs), rocPRIM's radix sort of the pairs, k_digest_entries
+ * (timestamps and checksums, written in sorted order).  The call waits once, at its end, for the counters below.
+ * The digest lives on the device until lamd_store_digest_free (before lamd_shutdown of its context); it does not refer to the image. */
+typedef struct lamd_store_digest lamd_store_digest;
+typedef struct {
+	uint64_t records;             /* n */
+	uint64_t channels;            /* channels seen */
+	uint64_t entries;             /* ... of them with at least one update: the digest's count */
+	uint64_t channels_no_update;  /* ... and without any */
+	uint64_t updates_no_channel, updates_in_front, updates_short;   /* counting 258 records ignored, by reason */
+	double stage_ms[5];           /* with lamd_set_timing: index, slots, channels, sort, entries */
+} lamd_store_digest_summary;
+int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
+				   const int8_t *verdict, lamd_store_digest **digest, lamd_store_digest_summary *summary);
+void lamd_store_digest_free(lamd_store_digest *digest);
+size_t lamd_store_digest_count(const lamd_store_digest *digest);
+/* copies the digest back: scid[cap], ts[2 * cap], csum[2 * cap], rec[3 * cap] (any may be NULL); cap < count: LAMD_ERR_ARG */
+int lamd_store_digest_read(const lamd_store_digest *digest, size_t cap, uint64_t *scid, uint32_t *ts, uint32_t *csum, uint32_t *rec);
+
+/* THE REPLIES.  Query q is the raw wire message queries + qoff[q] .. qoff[q + 1]: be16 263 | chain_hash 32 | be32 first_blocknum | be32
+ * number_of_blocks | TLV stream; TLV 1 = query_option, a bigsize, bit 0 asks for timestamps, bit 1 for checksums, other bits are ignored.
+ * The queries are parsed on the host by fromwire_tlv's rules (ascending types, minimal bigsize, an unknown even type fails, an unknown odd
+ * one is skipped).  status[q]:
+ *    0  answered
+ *   -1  malformed: no reply (the reference sends "Bad query_channel_range w/tlvs ..."; the caller owns that text)
+ *    1  foreign chain_hash: exactly one reply that echoes the query's chain_hash, first_blocknum and number_of_blocks as received, with
+ *       sync_complete 0, len 0 and no TLVs (:735-744)
+ * The replies of query q are the messages reply_first[q] .. reply_first[q + 1] - 1; message j is the bytes out + msg_off[j] .. msg_off[j + 1].
+ * msg_cap or out_cap too small: LAMD_ERR_ARG with summary->messages / summary->bytes = what is needed, status and reply_first filled in
+ * and nothing written to msg_off, out or d_out.  out and d_out both NULL: the sizes alone.
+ * SELECTION  if first + number overflows, number = UINT32_MAX - first (:746-748); end = first + number - 1; the entries whose scid >> 40
+ *            lies in [first, end], none when number == 0: two binary searches in the digest.
+ * LIMIT      max_entries() (:519-561): bytes = 65535 - 2 - 43, per_entry = 8; each option asked for subtracts 1 + bigsize_len(8186 * 8) = 4
+ *            and adds 8 to per_entry; bytes is capped by max_encoded_bytes when that is not 0 (dev_max_encoding_bytes) and raised to
+ *            per_entry when it falls below; limit = bytes / per_entry: 8186, 4092, 4092, 2728 without a cap.
+ * SPLIT      queue_channel_ranges() with its one out-of-bounds corner made definite.  s = the selected scids, off = 0; loop:
+ *              rem = count - off; if rem <= limit: n = rem, blocks = number; else n = limit; while n > 0 and block(s[off + n - 1]) ==
+ *              block(s[off + limit]): n--; if n == 0: n = limit (one block holds more than a message: the boundary is broken, as the
+ *              reference chooses to, but its loop reads s[off - 1]); blocks = block(s[off + n]) - first.
+ *              emit (first, blocks, entries off .. off + n, sync_complete = (blocks == number)); first += blocks, number -= blocks,
+ *              off += n; while number != 0.
+ *            A query with number == 0 or one that selects nothing gives one reply without entries, sync_complete 1.  The device loop is
+ *            bounded by count + 1 iterations.
+ * MESSAGE    (:372-426, wire/peer_wire.csv:400-412) be16 264 | chain_hash | be32 first | be32 blocks | u8 sync_complete | be16 1 + 8n | 0x00
+ *            (uncompressed) | n be64 scids | with bit 0: 0x01, bigsize 1 + 8n, 0x00, n x (be32 ts[0], be32 ts[1]) | with bit 1: 0x03,
+ *            bigsize 8n, n x (be32 csum[0], be32 csum[1]).  With n = 0 both TLVs are still there when asked for, type 1 with length 1 and
+ *            type 3 with length 0: send_reply_channel_range() hands over a non-NULL, zero-length checksums_tlv (tal_dup_arr of 0
+ *            elements, :410-413), the generated towire of a TLV record (tools/gen/impl_template:220-245) returns NULL only for a NULL
+ *            field and an empty array otherwise, and towire_tlv() (wire/tlvstream.c:350-362) writes type and length of whatever is not NULL.
+ * Device work: k_range_count (one lane per query: searches and split, counting), k_range_scan (messages and bytes per query to
+ * offsets), k_range_plan (the split again, writing (first, blocks, off, n, final, flags) and the offset of every message), then
+ * k_range_encode, one aligned 32-bit word of the output per lane, bytes swapped in registers.  The host waits once for sizes and
+ * offsets and once for the bytes. */
+typedef struct {
+	uint64_t answered, malformed, foreign;   /* queries by status */
+	uint64_t messages, bytes;                /* replies and their total size: what msg_cap and out_cap must hold */
+	double stage_ms[2];                      /* with lamd_set_timing: plan (count, scan, plan), encode */
+} lamd_range_reply_summary;
+int lamd_channel_range_reply_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, size_t nq, const uint8_t *queries,
+				   const uint64_t *qoff, uint32_t max_encoded_bytes, int8_t *status, uint64_t *reply_first, size_t msg_cap,
+				   uint64_t *msg_off, uint8_t *out, void *d_out, size_t out_cap, lamd_range_reply_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

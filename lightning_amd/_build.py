@@ -26,7 +26,7 @@ EXTRA = os.environ.get("LAMD_BUILD_FLAGS", "").split()
 
 # translation units of liblightning_amd.so: (source, everything it includes from this tree, flags)
 ENGINE_TUS = [
-    ("lamd_engine.hip", _H("verify_core.h", "group.h", "fe.h", "fe_asm.inc", "fuzz.h", "scalar.h", "sha256.h", "lamd_common.h", "bolt12.h", "host_ranges.h", "key_column.h", "store_audit.h", "store_repair.h", "store_latest.h", "bolt11.h", "table_audit.h", "bolt12_text.h") +
+    ("lamd_engine.hip", _H("verify_core.h", "group.h", "fe.h", "fe_asm.inc", "fuzz.h", "scalar.h", "sha256.h", "lamd_common.h", "bolt12.h", "host_ranges.h", "key_column.h", "store_audit.h", "store_repair.h", "store_latest.h", "store_digest.h", "bolt11.h", "table_audit.h", "bolt12_text.h") +
      _I("lightning_amd.h", "lightning_amd_debug.h"), HIPFLAGS + EXTRA),
     ("lamd_multi.cpp", _H("numa_cpus.h") + _I("lightning_amd.h", "lightning_amd_debug.h"), ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall"]),
 ]

@@ -52,6 +52,19 @@ class LamdStoreLatestSummary(ctypes.Structure):
                 ("dropped_stale", ctypes.c_uint64), ("out_len", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
 
 
+class LamdStoreDigestSummary(ctypes.Structure):
+    """lamd_store_digest_summary (include/lightning_amd.h): what lamd_gossip_store_digest_build reports about the digest it built"""
+    _fields_ = [("records", ctypes.c_uint64), ("channels", ctypes.c_uint64), ("entries", ctypes.c_uint64), ("channels_no_update", ctypes.c_uint64),
+                ("updates_no_channel", ctypes.c_uint64), ("updates_in_front", ctypes.c_uint64), ("updates_short", ctypes.c_uint64),
+                ("stage_ms", ctypes.c_double * 5)]
+
+
+class LamdRangeReplySummary(ctypes.Structure):
+    """lamd_range_reply_summary (include/lightning_amd.h): what lamd_channel_range_reply_batch reports about a batch of queries"""
+    _fields_ = [("answered", ctypes.c_uint64), ("malformed", ctypes.c_uint64), ("foreign", ctypes.c_uint64), ("messages", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 2)]
+
+
 class LamdGtableAuditResult(ctypes.Structure):
     """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
     _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
@@ -105,6 +118,13 @@ SYMBOLS = {
     "lamd_gossip_store_repair_latest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_u8p, ctypes.POINTER(LamdStoreLatestPolicy), c_sz, c_u8p, c_u8p,
                                                        c_u8p, c_u8p, ctypes.POINTER(c_sz), c_u8p, ctypes.c_void_p, c_sz, ctypes.POINTER(LamdStoreSummary),
                                                        ctypes.POINTER(LamdStoreLatestSummary)]),
+    "lamd_gossip_store_digest_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_void_p),
+                                                      ctypes.POINTER(LamdStoreDigestSummary)]),
+    "lamd_store_digest_free": (None, [ctypes.c_void_p]),
+    "lamd_store_digest_count": (c_sz, [ctypes.c_void_p]),
+    "lamd_store_digest_read": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p]),
+    "lamd_channel_range_reply_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
+                                                      ctypes.c_void_p, c_sz, ctypes.POINTER(LamdRangeReplySummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

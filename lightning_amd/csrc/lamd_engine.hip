@@ -24,6 +24,8 @@
 #include "store_audit.h"
 #include "store_repair.h"
 #include "store_latest.h"
+#include "store_digest.h"
+#include <rocprim/device/device_radix_sort.hpp>
 #include "bolt11.h"
 #include "table_audit.h"
 #include "bolt12_text.h"
@@ -809,6 +811,130 @@ __device__ __forceinline__ void block_alloc4(u32 *const counters[4], const bool 
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < 4; c++) pos[c] = s_base[wave][c] + pre[c];
+}
+
+// ---- gossip_store digest (lamd_gossip_store_digest_build; per-record and per-entry logic in store_digest.h).  One lane per record; each
+// stage reads what the one before wrote with atomics, so each is a launch of its own.  cnt: DIGEST_CNT_* counters, all 0; a wave adds
+// its count with one atomic.  keys / vals: (1 << bits) + 1 slots preset to all-ones bytes; slot: 2 * n words preset to 0.
+enum { DIGEST_CNT_ENTRIES = 0, DIGEST_CNT_CHANNELS = 1, DIGEST_CNT_NO_UPDATE = 2, DIGEST_CNT_NO_CHANNEL = 3, DIGEST_CNT_IN_FRONT = 4, DIGEST_CNT_SHORT = 5, DIGEST_CNTS = 8 };
+__device__ __forceinline__ void wave_count(u32 *counter, bool pred) {
+  const u64 mask = __ballot(pred);
+  if ((threadIdx.x & 63u) == 0 && mask) atomicAdd(counter, (u32)__popcll(mask));
+}
+__global__ void __launch_bounds__(256) k_digest_index(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                      const int8_t *__restrict__ verdict, u64 *keys, u32 *vals, u32 bits) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_digest_index_one(store, store_len, rec_off, verdict, i, keys, vals, bits);
+}
+__global__ void __launch_bounds__(256) k_digest_slots(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                      const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
+                                                      u32 bits, u32 *slot, u32 *cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  const u32 r = i < n ? store_digest_slot_one(store, store_len, rec_off, verdict, i, keys, vals, bits, slot) : (u32)STORE_DIGEST_UPD_NONE;
+  wave_count(&cnt[DIGEST_CNT_NO_CHANNEL], r == STORE_DIGEST_UPD_NO_CHANNEL);
+  wave_count(&cnt[DIGEST_CNT_IN_FRONT], r == STORE_DIGEST_UPD_IN_FRONT);
+  wave_count(&cnt[DIGEST_CNT_SHORT], r == STORE_DIGEST_UPD_SHORT);
+}
+// the channels with an update, compacted in any order as (scid, announcement index) pairs: pair_key / pair_val hold n pairs preset to
+// all-ones bytes, so that behind the cnt[DIGEST_CNT_ENTRIES] real pairs the largest key stands -- a stable sort of all n pairs leaves the
+// real ones in front, the scid of that value included
+__global__ void __launch_bounds__(256) k_digest_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                     const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
+                                                     u32 bits, const u32 *__restrict__ slot, u64 *__restrict__ pair_key, u32 *__restrict__ pair_val, u32 *cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  u64 scid = 0;
+  const u32 c = i < n ? store_digest_chan_one(store, store_len, rec_off, verdict, i, keys, vals, bits, slot, &scid) : 0u;
+  const u32 e = wave_alloc(&cnt[DIGEST_CNT_ENTRIES], c == 1, 0, nullptr);
+  if (c == 1 && e < n) {
+    pair_key[e] = scid;
+    pair_val[e] = i;
+  }
+  wave_count(&cnt[DIGEST_CNT_CHANNELS], c != 0);
+  wave_count(&cnt[DIGEST_CNT_NO_UPDATE], c == 2);
+}
+// entry j of the sorted digest, j < cnt[DIGEST_CNT_ENTRIES] (the grid covers n): ann[j] = its announcement.  The CRC tables as in k_store_crc.
+__global__ void __launch_bounds__(256) k_digest_entries(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                        const u32 *__restrict__ slot, const u32 *__restrict__ ann, const u32 *__restrict__ cnt,
+                                                        u32 *__restrict__ ts, u32 *__restrict__ csum, u32 *__restrict__ rec) {
+  __shared__ u32 T[4 * 256];
+  const u32 t = threadIdx.x;
+  u32 v = store_crc_t0(t);
+  T[t] = v;
+  __syncthreads();
+  for (int k = 1; k < 4; k++) {
+    v = (v >> 8) ^ T[v & 0xff];
+    T[256 * k + t] = v;
+  }
+  __syncthreads();
+  const u32 j = blockIdx.x * 256 + t, count = cnt[DIGEST_CNT_ENTRIES] < n ? cnt[DIGEST_CNT_ENTRIES] : n;
+  if (j >= count) return;
+  const u32 a = ann[j];
+  if (a >= n) return;   // (never: the first `count` pairs are real)
+  store_digest_entry_one<4>(T, store, store_len, rec_off, a, slot, ts + 2 * (size_t)j, csum + 2 * (size_t)j, rec + 3 * (size_t)j);
+}
+
+// ---- query_channel_range answers (lamd_channel_range_reply_batch; per-query and per-word logic in store_digest.h).
+// k_range_count: one lane per query runs the searches and the split and leaves the number of its replies and of their bytes.
+__global__ void __launch_bounds__(256) k_range_count(u32 nq, const store_range_query *__restrict__ queries, const u64 *__restrict__ scid, u32 count,
+                                                     u32 *__restrict__ n_msgs, u64 *__restrict__ n_bytes) {
+  const u32 q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  const store_range_total t = store_range_plan(queries[q], q, scid, count, nullptr, 0);
+  n_msgs[q] = t.msgs;
+  n_bytes[q] = t.bytes;
+}
+// k_range_scan: ONE block; the exclusive scans of both arrays, tile by tile with a carry: msg_first[nq + 1], byte_first[nq + 1]
+__global__ void __launch_bounds__(256) k_range_scan(u32 nq, const u32 *__restrict__ n_msgs, const u64 *__restrict__ n_bytes, u64 *__restrict__ msg_first,
+                                                    u64 *__restrict__ byte_first) {
+  __shared__ u64 sm[256], sb[256];
+  const u32 t = threadIdx.x;
+  u64 cm = 0, cb = 0;
+  for (u32 base = 0; base <= nq; base += 256) {
+    const u32 q = base + t;
+    const u64 vm = q < nq ? (u64)n_msgs[q] : 0, vb = q < nq ? n_bytes[q] : 0;
+    sm[t] = vm;
+    sb[t] = vb;
+    __syncthreads();
+    for (u32 d = 1; d < 256; d <<= 1) {
+      const u64 am = t >= d ? sm[t - d] : 0, ab = t >= d ? sb[t - d] : 0;
+      __syncthreads();
+      sm[t] += am;
+      sb[t] += ab;
+      __syncthreads();
+    }
+    if (q <= nq) {
+      msg_first[q] = cm + sm[t] - vm;
+      byte_first[q] = cb + sb[t] - vb;
+    }
+    cm += sm[255];
+    cb += sb[255];
+    __syncthreads();
+  }
+}
+// k_range_plan: the split again, now writing: the replies of query q are msgs[msg_first[q] ..], as far as they lie below msg_cap, and
+// msg_off[j] their offsets in the output; the last query's lane closes msg_off with the total
+__global__ void __launch_bounds__(256) k_range_plan(u32 nq, const store_range_query *__restrict__ queries, const u64 *__restrict__ scid, u32 count,
+                                                    const u64 *__restrict__ msg_first, const u64 *__restrict__ byte_first, u64 msg_cap,
+                                                    store_range_msg *__restrict__ msgs, u64 *__restrict__ msg_off) {
+  const u32 q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  const u64 j0 = msg_first[q];
+  if (q == nq - 1 && msg_first[nq] <= msg_cap) msg_off[msg_first[nq]] = byte_first[nq];
+  if (j0 >= msg_cap) return;
+  const u64 room = msg_cap - j0;
+  const store_range_query qu = queries[q];
+  const store_range_total t = store_range_plan(qu, q, scid, count, msgs + j0, room < 0xFFFFFFFFull ? (u32)room : 0xFFFFFFFFu);
+  u64 off = byte_first[q];
+  for (u32 k = 0; k < t.msgs && k < room; k++) {
+    msg_off[j0 + k] = off;
+    off += store_range_msg_bytes(qu, msgs[j0 + k].n);
+  }
+}
+// k_range_encode: one aligned 32-bit word of the output per lane
+__global__ void __launch_bounds__(256) k_range_encode(u64 words, const store_range_msg *__restrict__ msgs, const u64 *__restrict__ msg_off, u32 n_msgs,
+                                                      const store_range_query *__restrict__ queries, store_digest_view d, u8 *__restrict__ out, u64 total) {
+  const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (k < words) store_range_word(msgs, msg_off, n_msgs, queries, d, out, total, (u32)((uintptr_t)out & 3), k);
 }
 
 // Key-table cache.  One entry per distinct public key that has a comb table: the serialised key bytes
@@ -1865,6 +1991,8 @@ struct lamd_ctx {
   hipEvent_t ev_store[6] = {};                      // ... and its stage boundaries (created when a timed audit first runs)
   devbuf st_rep, st_pack;                           // gossip_store repair: reasons, sizes, offsets, block sums, node table; the output image
   hipEvent_t ev_rep[4] = {};                        // ... and its stage boundaries
+  devbuf st_dig, st_rng, st_rng_out;                // digest build: its tables and the sort's workspace; range replies: plan arrays, the messages
+  hipEvent_t ev_dig[6] = {};                        // ... and the stage boundaries of either call
   devbuf tx_cols;                                   // text front ends (lamd_bolt11_check_batch, lamd_checkmessage_batch): the per-row columns
   hipEvent_t ev_text[3] = {};                       // ... in front of the front-end kernel, behind it, behind the merge (created when a timed call first runs)
   double text_ms[2] = {0, 0};                       // ... and what they measured last: front end, curve work + merge
@@ -2250,8 +2378,10 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
   for (devbuf *b : {&ctx->small_done, &ctx->recs, &ctx->qwords, &ctx->keyok, &ctx->slots, &ctx->vbuf, &ctx->in_a, &ctx->in_b, &ctx->in_c, &ctx->out,
                     &ctx->g_msgs, &ctx->g_off, &ctx->g_ids, &ctx->g_rowbase, &ctx->g_hash, &ctx->g_sig, &ctx->g_pub,
                     &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict, &ctx->st_img, &ctx->st_host, &ctx->st_ids, &ctx->st_tab, &ctx->st_out, &ctx->st_rep,
-                    &ctx->st_pack, &ctx->tx_cols})
+                    &ctx->st_pack, &ctx->st_dig, &ctx->st_rng, &ctx->st_rng_out, &ctx->tx_cols})
     release(b);
+  for (auto &e : ctx->ev_dig)
+    if (e) (void)hipEventDestroy(e);
   for (auto &e : ctx->ev_text)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : ctx->ev_store)
@@ -4554,6 +4684,214 @@ extern "C" int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *sto
   latest->dropped_timestamp = counts[STORE_DROP_TIMESTAMP];
   latest->dropped_stale = counts[STORE_DROP_STALE];
   return rc;
+}
+
+// ---- the channel digest of a store image, and query_channel_range answered from it.  Both calls run on the context's own stream.
+struct lamd_store_digest {
+  lamd_ctx *ctx = nullptr;
+  void *mem = nullptr;        // scid u64[cap] | ts u32[2 cap] | csum u32[2 cap] | rec u32[3 cap]
+  u64 *scid = nullptr;
+  u32 *ts = nullptr, *csum = nullptr, *rec = nullptr;
+  size_t cap = 0, count = 0;  // cap = the records of the store: the sort runs over that many pairs
+};
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+extern "C" void lamd_store_digest_free(lamd_store_digest *d) {
+  if (!d) return;
+  if (d->mem) {
+    (void)hipSetDevice(d->ctx->device);
+    (void)hipFree(d->mem);
+  }
+  delete d;
+}
+extern "C" size_t lamd_store_digest_count(const lamd_store_digest *d) { return d ? d->count : 0; }
+extern "C" int lamd_store_digest_read(const lamd_store_digest *d, size_t cap, uint64_t *scid, uint32_t *ts, uint32_t *csum, uint32_t *rec) {
+  if (!d) return LAMD_ERR_ARG;
+  lamd_ctx *ctx = d->ctx;
+  if (cap < d->count) { ctx->err = "gossip_store digest: arrays too small"; return LAMD_ERR_ARG; }
+  if (d->count == 0) return LAMD_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (scid) HIPCHK(ctx, hipMemcpy(scid, d->scid, 8 * d->count, hipMemcpyDeviceToHost));
+  if (ts) HIPCHK(ctx, hipMemcpy(ts, d->ts, 8 * d->count, hipMemcpyDeviceToHost));
+  if (csum) HIPCHK(ctx, hipMemcpy(csum, d->csum, 8 * d->count, hipMemcpyDeviceToHost));
+  if (rec) HIPCHK(ctx, hipMemcpy(rec, d->rec, 12 * d->count, hipMemcpyDeviceToHost));
+  return LAMD_OK;
+}
+extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
+                                              const int8_t *verdict, lamd_store_digest **digest, lamd_store_digest_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (digest) *digest = nullptr;
+  if ((!store && !d_store) || !digest || !summary || (n && !rec_off)) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  if (n >= (size_t)STORE_NONE / 2) { ctx->err = "gossip_store digest: too many records"; return LAMD_ERR_ARG; }
+  *summary = lamd_store_digest_summary();
+  summary->records = n;
+  lamd_store_digest *D = new (std::nothrow) lamd_store_digest();
+  if (!D) return LAMD_ERR_NOMEM;
+  D->ctx = ctx;
+  D->cap = n;
+  if (n == 0) { *digest = D; return LAMD_OK; }
+  lamd_ctx *L = ctx;
+  hipStream_t st = ctx->stream;
+  auto fail = [&](int code) {   // queued copies read the caller's arrays
+    (void)hipStreamSynchronize(st);
+    lamd_store_digest_free(D);
+    return code;
+  };
+  hipError_t e0 = hipSetDevice(ctx->device);
+  if (e0 == hipSuccess) e0 = hipMalloc(&D->mem, 36 * n);
+  if (e0 != hipSuccess) { ctx->err = std::string("gossip_store digest: ") + hipGetErrorString(e0); return fail(e0 == hipErrorOutOfMemory ? LAMD_ERR_NOMEM : LAMD_ERR_HIP); }
+  D->scid = (u64 *)D->mem;
+  D->ts = (u32 *)(D->scid + n);
+  D->csum = D->ts + 2 * n;
+  D->rec = D->csum + 2 * n;
+  u32 bits = 1;
+  while (((size_t)1 << bits) < 2 * n) bits++;
+  const size_t slots = ((size_t)1 << bits) + 1;
+  size_t sort_bytes = 0;
+  STCHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 64, st));
+  // rec_off u64[n] | pair_key u64[n] | keys u64[slots] | vals u32[slots] | slot u32[2 n] | pair_val u32[n] | ann u32[n] | cnt u32[DIGEST_CNTS] | verdict i8[n] |
+  // (256-aligned) the sort's workspace
+  const size_t o_sort = align_up(8 * (2 * n + slots) + 4 * (slots + 4 * n + DIGEST_CNTS) + n, 256);
+  int rc;
+  if ((rc = ensure(ctx, &ctx->st_dig, o_sort + sort_bytes + 16)) != LAMD_OK) return fail(rc);
+  if (!d_store && (rc = ensure(ctx, &ctx->st_img, len + 16)) != LAMD_OK) return fail(rc);
+  const bool timed = ctx->timing;
+  if (timed)
+    for (auto &e : ctx->ev_dig)
+      if (!e) STCHK(hipEventCreate(&e));
+  u64 *d_recoff = ctx->st_dig.as<u64>(), *d_pkey = d_recoff + n, *d_keys = d_pkey + n;
+  u32 *d_vals = (u32 *)(d_keys + slots), *d_slot = d_vals + slots, *d_pval = d_slot + 2 * n, *d_ann = d_pval + n, *d_cnt = d_ann + n;
+  int8_t *d_verdict = verdict ? (int8_t *)(d_cnt + DIGEST_CNTS) : nullptr;
+  void *d_sort = ctx->st_dig.as<u8>() + o_sort;
+  const u8 *img = (const u8 *)d_store;
+  if (!d_store) {
+    STCHK(hipMemcpyAsync(ctx->st_img.p, store, len, hipMemcpyHostToDevice, st));
+    img = ctx->st_img.as<const u8>();
+  }
+  STCHK(hipMemcpyAsync(d_recoff, rec_off, 8 * n, hipMemcpyHostToDevice, st));
+  if (verdict) STCHK(hipMemcpyAsync(d_verdict, verdict, n, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(d_pkey, 0xFF, 8 * (n + slots) + 4 * slots, st));   // pair_key, keys, vals
+  STCHK(hipMemsetAsync(d_slot, 0, 8 * n, st));
+  STCHK(hipMemsetAsync(d_pval, 0xFF, 4 * n, st));
+  STCHK(hipMemsetAsync(d_cnt, 0, 4 * DIGEST_CNTS, st));
+  const dim3 grid(blocks_for(n)), block(256);
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[0], st));
+  hipLaunchKernelGGL(k_digest_index, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, d_keys, d_vals, bits);
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[1], st));
+  hipLaunchKernelGGL(k_digest_slots, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, (const u64 *)d_keys, (const u32 *)d_vals,
+                     bits, d_slot, d_cnt);
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[2], st));
+  hipLaunchKernelGGL(k_digest_chan, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, (const u64 *)d_keys, (const u32 *)d_vals,
+                     bits, (const u32 *)d_slot, d_pkey, d_pval, d_cnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[3], st));
+  STCHK(rocprim::radix_sort_pairs(d_sort, sort_bytes, (const u64 *)d_pkey, D->scid, (const u32 *)d_pval, d_ann, n, 0, 64, st));
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[4], st));
+  hipLaunchKernelGGL(k_digest_entries, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const u32 *)d_slot, (const u32 *)d_ann, (const u32 *)d_cnt, D->ts,
+                     D->csum, D->rec);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[5], st));
+  u32 cnt[DIGEST_CNTS] = {};
+  STCHK(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed)
+    for (int k = 0; k < 5; k++) {
+      float ms = 0;
+      STCHK(hipEventElapsedTime(&ms, ctx->ev_dig[k], ctx->ev_dig[k + 1]));
+      summary->stage_ms[k] = ms;
+    }
+  D->count = cnt[DIGEST_CNT_ENTRIES];
+  summary->entries = cnt[DIGEST_CNT_ENTRIES];
+  summary->channels = cnt[DIGEST_CNT_CHANNELS];
+  summary->channels_no_update = cnt[DIGEST_CNT_NO_UPDATE];
+  summary->updates_no_channel = cnt[DIGEST_CNT_NO_CHANNEL];
+  summary->updates_in_front = cnt[DIGEST_CNT_IN_FRONT];
+  summary->updates_short = cnt[DIGEST_CNT_SHORT];
+  *digest = D;
+  return LAMD_OK;
+}
+
+extern "C" int lamd_channel_range_reply_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, size_t nq, const uint8_t *queries,
+                                              const uint64_t *qoff, uint32_t max_encoded_bytes, int8_t *status, uint64_t *reply_first, size_t msg_cap,
+                                              uint64_t *msg_off, uint8_t *out, void *d_out, size_t out_cap, lamd_range_reply_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!digest || digest->ctx != ctx || !chain_hash32 || !summary || !reply_first || (nq && (!queries || !qoff || !status)) || (msg_cap && !msg_off) ||
+      nq >= (size_t)STORE_NONE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_range_reply_summary();
+  reply_first[0] = 0;
+  if (nq == 0) {
+    if (msg_cap) msg_off[0] = 0;
+    return LAMD_OK;
+  }
+  std::vector<store_range_query> qs(nq);
+  for (size_t q = 0; q < nq; q++) {
+    if (qoff[q + 1] < qoff[q]) { ctx->err = "channel_range replies: decreasing query offsets"; return LAMD_ERR_ARG; }
+    qs[q] = store_range_parse(queries + qoff[q], (size_t)(qoff[q + 1] - qoff[q]), chain_hash32, max_encoded_bytes);
+    status[q] = (int8_t)qs[q].kind;
+    (qs[q].kind == STORE_RANGE_ANSWERED ? summary->answered : qs[q].kind == STORE_RANGE_FOREIGN ? summary->foreign : summary->malformed)++;
+  }
+  lamd_ctx *L = ctx;
+  hipStream_t st = ctx->stream;
+  auto fail = [&](int code) {   // queued copies read this frame's vectors
+    (void)hipStreamSynchronize(st);
+    return code;
+  };
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const u32 count = (u32)digest->count;
+  // no query has more than count + 1 replies: the device arrays need not follow a generous msg_cap
+  const u64 most = (u64)nq * ((u64)count + 1), cap_dev = msg_cap < most ? msg_cap : most;
+  // msg_first u64[nq + 1] | byte_first u64[nq + 1] | n_bytes u64[nq] | msg_off u64[cap_dev + 1] | queries[nq] | msgs[cap_dev] | n_msgs u32[nq]
+  int rc;
+  if ((rc = ensure(ctx, &ctx->st_rng, 8 * (3 * nq + 2 + cap_dev + 1) + sizeof(store_range_query) * nq + sizeof(store_range_msg) * cap_dev + 4 * nq + 16)) != LAMD_OK)
+    return rc;
+  const bool timed = ctx->timing;
+  if (timed)
+    for (auto &e : ctx->ev_dig)
+      if (!e) HIPCHK(ctx, hipEventCreate(&e));
+  u64 *d_mfirst = ctx->st_rng.as<u64>(), *d_bfirst = d_mfirst + nq + 1, *d_nbytes = d_bfirst + nq + 1, *d_msgoff = d_nbytes + nq;
+  store_range_query *d_qs = (store_range_query *)(d_msgoff + cap_dev + 1);
+  store_range_msg *d_msgs = (store_range_msg *)(d_qs + nq);
+  u32 *d_nmsgs = (u32 *)(d_msgs + cap_dev);
+  std::vector<u64> h_first(2 * (nq + 1)), h_msgoff(cap_dev + 1);
+  const dim3 grid(blocks_for(nq)), block(256);
+  STCHK(hipMemcpyAsync(d_qs, qs.data(), sizeof(store_range_query) * nq, hipMemcpyHostToDevice, st));
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[0], st));
+  hipLaunchKernelGGL(k_range_count, grid, block, 0, st, (u32)nq, (const store_range_query *)d_qs, (const u64 *)digest->scid, count, d_nmsgs, d_nbytes);
+  hipLaunchKernelGGL(k_range_scan, dim3(1), block, 0, st, (u32)nq, (const u32 *)d_nmsgs, (const u64 *)d_nbytes, d_mfirst, d_bfirst);
+  hipLaunchKernelGGL(k_range_plan, grid, block, 0, st, (u32)nq, (const store_range_query *)d_qs, (const u64 *)digest->scid, count, (const u64 *)d_mfirst,
+                     (const u64 *)d_bfirst, (u64)cap_dev, d_msgs, d_msgoff);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[1], st));
+  STCHK(hipMemcpyAsync(h_first.data(), d_mfirst, 16 * (nq + 1), hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(h_msgoff.data(), d_msgoff, 8 * (cap_dev + 1), hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  const u64 n_msgs = h_first[nq], total = h_first[2 * nq + 1];
+  summary->messages = n_msgs;
+  summary->bytes = total;
+  memcpy(reply_first, h_first.data(), 8 * (nq + 1));
+  if (n_msgs > msg_cap) { ctx->err = "channel_range replies: msg_off too small"; return LAMD_ERR_ARG; }
+  const bool want_out = out || d_out;
+  if (want_out && total > out_cap) { ctx->err = "channel_range replies: output buffer too small"; return LAMD_ERR_ARG; }
+  if (msg_off) memcpy(msg_off, h_msgoff.data(), 8 * (n_msgs + 1));
+  if (!want_out || n_msgs == 0) return LAMD_OK;
+  if (!d_out && (rc = ensure(ctx, &ctx->st_rng_out, total + 16)) != LAMD_OK) return rc;
+  u8 *d_bytes = d_out ? (u8 *)d_out : ctx->st_rng_out.as<u8>();
+  const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+  hipLaunchKernelGGL(k_range_encode, dim3((unsigned)((words + 255) / 256)), block, 0, st, words, (const store_range_msg *)d_msgs, (const u64 *)d_msgoff, (u32)n_msgs,
+                     (const store_range_query *)d_qs, store_digest_view{digest->scid, digest->ts, digest->csum}, d_bytes, total);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(hipEventRecord(ctx->ev_dig[2], st));
+  if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed)
+    for (int k = 0; k < 2; k++) {
+      float ms = 0;
+      STCHK(hipEventElapsedTime(&ms, ctx->ev_dig[k], ctx->ev_dig[k + 1]));
+      summary->stage_ms[k] = ms;
+    }
+  return LAMD_OK;
 }
 #undef STCHK
 

@@ -79,6 +79,36 @@ def gossip_store_frame(blob):
     return off[:n.value], _store_summary(s)
 
 
+class StoreDigest:
+    """lamd_store_digest: the channel digest Engine.gossip_store_digest built, resident on the device.  close() it before its Engine."""
+
+    def __init__(self, engine, handle, summary):
+        self._eng, self._h = engine, handle
+        self.summary = {k: (list(getattr(summary, k)) if k == "stage_ms" else int(getattr(summary, k))) for k, _ in summary._fields_}
+
+    def __len__(self):
+        return int(self._eng._lib.lamd_store_digest_count(self._h)) if self._h else 0
+
+    def read(self):
+        """-> (scid uint64 [count], ts uint32 [count, 2], csum uint32 [count, 2], rec uint32 [count, 3] (0xFFFFFFFF: none))"""
+        n = len(self)
+        scid, ts, csum, rec = (np.zeros(max(1, n), dtype=np.uint64), np.zeros((max(1, n), 2), dtype=np.uint32), np.zeros((max(1, n), 2), dtype=np.uint32),
+                               np.zeros((max(1, n), 3), dtype=np.uint32))
+        self._eng._chk(self._eng._lib.lamd_store_digest_read(self._h, n, scid.ctypes.data, ts.ctypes.data, csum.ctypes.data, rec.ctypes.data))
+        return scid[:n], ts[:n], csum[:n], rec[:n]
+
+    def close(self):
+        if self._h:
+            self._eng._lib.lamd_store_digest_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class Engine:
     """One context = one GPU, one stream.  Mirrors lamd_init()/lamd_shutdown()."""
 
@@ -418,6 +448,64 @@ class Engine:
         k = cnt.value
         return (out[:r.out_len].tobytes() if host_out else None, off[:k], verdict[:k], new_off[:k], reason[:k], _store_summary(s),
                 _repair_summary(r) if policy is None else _latest_summary(r))
+
+    def gossip_store_digest(self, blob=None, rec_off=None, verdict=None, d_store=None):
+        """lamd_gossip_store_digest_build: the channel digest of a gossip_store image, resident on the device: one entry per channel with an
+        update (scid, both timestamps, both update checksums, the record indices), sorted by scid.  blob: the image (bytes or numpy uint8),
+        and / or d_store: the image in a torch uint8 CUDA tensor (read in place); rec_off: the records' offsets (default: the walk over
+        blob); verdict: optional int8 per record, the audit's -- records that are not OK do not count.  -> StoreDigest"""
+        if blob is None and d_store is None:
+            raise ValueError("an image on the host or on the device is needed")
+        buf_ptr, n_bytes = None, 0
+        if blob is not None:
+            _, n_bytes, buf = _store_blob(blob)
+            buf_ptr = buf.ctypes.data
+            if rec_off is None:
+                rec_off = gossip_store_frame(blob)[0]
+        if rec_off is None:
+            raise ValueError("a resident image needs rec_off")
+        d_ptr = None
+        if d_store is not None:
+            if blob is not None and d_store.numel() != n_bytes:
+                raise ValueError("the resident image and the host image differ in size")
+            n_bytes = d_store.numel()
+            self._after_torch()
+            d_ptr = d_store.data_ptr()
+        off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        v = None
+        if verdict is not None:
+            v = np.ascontiguousarray(verdict, dtype=np.int8)
+            if v.size != off.size:
+                raise ValueError("one verdict per record")
+        h, s = ctypes.c_void_p(), _ffi.LamdStoreDigestSummary()
+        self._chk(self._lib.lamd_gossip_store_digest_build(self._ctx, buf_ptr, n_bytes, d_ptr, off.size, off.ctypes.data if off.size else None,
+                                                           v.ctypes.data if v is not None and v.size else None, ctypes.byref(h), ctypes.byref(s)))
+        return StoreDigest(self, h, s)
+
+    def channel_range_replies(self, digest, chain_hash, queries, max_encoded_bytes=0, return_summary=False):
+        """lamd_channel_range_reply_batch: the reply_channel_range messages to a batch of raw query_channel_range messages, from a
+        StoreDigest.  chain_hash: the 32 bytes of the chain this node serves; max_encoded_bytes: the reference's dev_max_encoding_bytes
+        (0: none).  -> (status int8 [queries] (0 answered, -1 malformed: no reply, 1 foreign chain: one empty reply), [[bytes, ...], ...])"""
+        chain = np.frombuffer(bytes(chain_hash), dtype=np.uint8)
+        if chain.size != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        nq = len(queries)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(bytes(q) for q in queries) + b"\x00", dtype=np.uint8)
+        status, first = np.zeros(max(1, nq), dtype=np.int8), np.zeros(nq + 1, dtype=np.uint64)
+        s = _ffi.LamdRangeReplySummary()
+        head = (self._ctx, digest._h, chain.ctypes.data, nq, blob.ctypes.data, qoff.ctypes.data, int(max_encoded_bytes), status.ctypes.data, first.ctypes.data)
+        rc = self._lib.lamd_channel_range_reply_batch(*head, 0, None, None, None, 0, ctypes.byref(s))          # the sizes
+        if rc < 0 and not (rc == -3 and s.messages):
+            self._chk(rc)
+        msg_off, out = np.zeros(s.messages + 1, dtype=np.uint64), np.zeros(max(1, s.bytes), dtype=np.uint8)
+        self._chk(self._lib.lamd_channel_range_reply_batch(*head, s.messages, msg_off.ctypes.data, out.ctypes.data, None, s.bytes, ctypes.byref(s)))
+        raw = out.tobytes()
+        replies = [[raw[int(msg_off[j]):int(msg_off[j + 1])] for j in range(int(first[q]), int(first[q + 1]))] for q in range(nq)]
+        if return_summary:
+            return status[:nq], replies, {k: (list(getattr(s, k)) if k == "stage_ms" else int(getattr(s, k))) for k, _ in s._fields_}
+        return status[:nq], replies
 
     # ---- single-item veneers (reference semantics)
     def check_signed_hash(self, hash32, sig64, pubkey):
