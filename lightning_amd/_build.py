@@ -1,12 +1,19 @@
 """Builds liblightning_amd.so (+ the host mirror and the test-traffic library) in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-One object per translation unit under lightning_amd/build/, then one link: a change to the multi-device layer (lamd_multi.cpp, seconds) does
-not recompile the kernels (lamd_engine.hip, minutes).  Staleness is decided by CONTENT: every artefact has a stamp file holding the sha256 of
-its sources, its flags and its inputs' stamps; file times play no part (a snapshot copied to the GPU box keeps the stamps next to the
-libraries, so nothing is rebuilt there)."""
+One object per translation unit under lightning_amd/build/, then one link: a change to the gossip_store headers recompiles lamd_store.hip, not
+the ecmult kernels of lamd_engine.hip; stale units compile side by side.  What a unit depends on is read from its #include "..." lines,
+followed through the tree.  Staleness is decided by CONTENT: every artefact has a stamp file holding the sha256 of its sources, its flags and
+its inputs' stamps; file times play no part (a snapshot copied to the GPU box keeps the stamps next to the libraries, so nothing is rebuilt
+there).
+
+python -m lightning_amd._build variant NAME FLAGS...: the engine with extra compile flags as tools/variants/liblightning_amd_NAME.so
+(tools/build_variant.sh)."""
 import hashlib
 import os
+import re
 import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -24,17 +31,37 @@ _I = lambda *names: [os.path.join(INC, f) for f in names]
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wno-unknown-pragmas", "-mllvm", "-amdgpu-codegenprepare-mul24=false"]
 EXTRA = os.environ.get("LAMD_BUILD_FLAGS", "").split()
 
-# translation units of liblightning_amd.so: (source, everything it includes from this tree, flags)
-ENGINE_TUS = [
-    ("lamd_engine.hip", _H("verify_core.h", "group.h", "fe.h", "fe_asm.inc", "fuzz.h", "scalar.h", "sha256.h", "lamd_common.h", "bolt12.h", "host_ranges.h", "key_column.h", "store_audit.h", "store_repair.h", "store_latest.h", "store_digest.h", "bolt11.h", "table_audit.h", "bolt12_text.h") +
-     _I("lightning_amd.h", "lightning_amd_debug.h"), HIPFLAGS + EXTRA),
-    ("lamd_multi.cpp", _H("numa_cpus.h") + _I("lightning_amd.h", "lightning_amd_debug.h"), ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall"]),
-]
-SOURCES = sorted({os.path.join(CSRC, tu[0]) for tu in ENGINE_TUS} | {h for tu in ENGINE_TUS for h in tu[1]})
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def includes(path, seen=None):
+    """every file of this tree that `path` includes, directly or through another header (sorted; `path` itself is not in the list)"""
+    seen = {} if seen is None else seen
+    with open(path, encoding="utf-8", errors="replace") as f:
+        text = f.read()
+    for name in _INCLUDE.findall(text):
+        dep = os.path.normpath(os.path.join(os.path.dirname(path), name))
+        if dep not in seen and dep.startswith(ROOT + os.sep) and os.path.exists(dep):
+            seen[dep] = True
+            includes(dep, seen)
+    return sorted(seen)
+
+
+# translation units of liblightning_amd.so and their flags: every unit with device code takes the ONE HIPFLAGS list (the mul24 workaround reaches
+# each of them).  lamd_engine.hip: the core; lamd_store.hip: the gossip_store calls; lamd_frontends.hip: transactions, TLV streams and text in front
+# of the core; lamd_debug.hip: the debuggers.  (lamd_testgen.hip is a library of its own, below.)
+MULTI_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall"]
+ENGINE_TUS = [(src, HIPFLAGS + EXTRA) for src in ("lamd_engine.hip", "lamd_store.hip", "lamd_frontends.hip", "lamd_debug.hip")] + [("lamd_multi.cpp", MULTI_FLAGS)]
+MAX_COMPILES = 16
+
+
+def unit_deps(src):
+    return includes(os.path.join(CSRC, src))
+
 
 # test / bench infrastructure: the synthetic-workload signer kernels (include/lightning_amd_testgen.h)
 TESTGEN = os.path.join(PKG, "liblightning_amd_testgen.so")
-TESTGEN_SOURCES = _H("lamd_testgen.hip", "verify_core.h", "group.h", "fe.h", "fe_asm.inc", "scalar.h", "sha256.h", "lamd_common.h") + _I("lightning_amd_testgen.h")
+TESTGEN_SOURCES = _H("lamd_testgen.hip") + includes(os.path.join(CSRC, "lamd_testgen.hip"))
 
 SHIM = os.path.join(PKG, "liblightning_amd_cln.so")
 SHIM_CPP = _H("cln_shim.cpp", "gossip_ingest.cpp")
@@ -69,7 +96,39 @@ def _hipcc():
 
 
 def _engine_digests():
-    return [(src, _digest([os.path.join(CSRC, src)] + deps, flags), flags) for src, deps, flags in ENGINE_TUS]
+    return [(src, _digest([os.path.join(CSRC, src)] + unit_deps(src), flags), flags) for src, flags in ENGINE_TUS]
+
+
+def _jobs(n):
+    """concurrent compiles: one per stale unit, MAX_COMPILES at the most, MAX_JOBS where the environment sets it"""
+    try:
+        limit = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        limit = MAX_COMPILES
+    return max(1, min(n, MAX_COMPILES, limit))
+
+
+def _compile_units(units, verbose=False):
+    """units: (command, object, digest); each object is stamped as it lands.  A unit that fails does not stop the others: its error is raised when
+    they have finished (their objects and stamps stay, so the next build compiles the failed unit alone); verbose command lines may interleave"""
+    def one(u):
+        cmd, obj, digest = u
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+        os.replace(obj + ".tmp", obj)
+        if digest:
+            _stamp(obj, digest)
+    if units:
+        with ThreadPoolExecutor(max_workers=_jobs(len(units))) as pool:
+            list(pool.map(one, units))
+
+
+def _link(objs, out, verbose=False):
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", out] + objs + ["-ldl"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
 
 
 def is_stale():
@@ -143,25 +202,42 @@ def build(force=False, verbose=False):
         build_served()
         return LIB
     os.makedirs(OBJDIR, exist_ok=True)
-    objs = []
+    objs, stale = [], []
     for src, digest, flags in tus:
         obj = os.path.join(OBJDIR, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
-        if not force and _fresh(obj, digest):
-            continue
-        cmd = [_hipcc()] + flags + ["-c", "-o", obj + ".tmp", os.path.join(CSRC, src)]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-        os.replace(obj + ".tmp", obj)
-        _stamp(obj, digest)
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", LIB + ".tmp"] + objs + ["-ldl"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
+        if force or not _fresh(obj, digest):
+            stale.append(([_hipcc()] + flags + ["-c", "-o", obj + ".tmp", os.path.join(CSRC, src)], obj, digest))
+    _compile_units(stale, verbose)
+    _link(objs, LIB + ".tmp", verbose)
     os.replace(LIB + ".tmp", LIB)
     _stamp(LIB, link_digest)
     build_shim(force=True)
     build_testgen()
     build_served()
     return LIB
+
+
+def build_variant(name, extra):
+    """the engine's units with `extra` behind their own flags, linked into tools/variants/liblightning_amd_NAME.so: the shipped library, its objects
+    and its stamps are not touched"""
+    out = os.path.join(ROOT, "tools", "variants")
+    os.makedirs(out, exist_ok=True)
+    objs, units = [], []
+    for src, flags in ENGINE_TUS:
+        obj = os.path.join(out, "%s_%s.o" % (os.path.splitext(src)[0], name))
+        objs.append(obj)
+        units.append(([_hipcc()] + flags + (extra if src.endswith(".hip") else []) + ["-c", "-o", obj + ".tmp", os.path.join(CSRC, src)], obj, None))
+    _compile_units(units, verbose=True)
+    lib = os.path.join(out, "liblightning_amd_%s.so" % name)
+    _link(objs, lib, verbose=True)
+    for obj in objs:
+        os.remove(obj)
+    return lib
+
+
+if __name__ == "__main__":
+    if len(sys.argv) >= 3 and sys.argv[1] == "variant":
+        print(build_variant(sys.argv[2], sys.argv[3:]))
+    else:
+        sys.exit("usage: python -m lightning_amd._build variant NAME [FLAGS...]")

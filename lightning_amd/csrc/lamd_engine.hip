@@ -1,38 +1,13 @@
 // liblightning_amd.so: HIP kernels (gfx950) + the C-ABI engine of include/lightning_amd.h.
 // One signature per wavefront lane in every kernel; the arithmetic lives in verify_core.h.
 // There is deliberately no CPU verification path in this library.
-#include <hip/hip_runtime.h>
-#include <type_traits>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <map>
-#include <mutex>
-#include <random>
-#include <string>
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "../../include/lightning_amd.h"
-#include "../../include/lightning_amd_debug.h"
-#include "verify_core.h"
+#include "engine_internal.h"
 #include "fuzz.h"
 #include "host_ranges.h"
 #include "key_column.h"
-#include "store_audit.h"
-#include "store_repair.h"
-#include "store_latest.h"
-#include "store_digest.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include "bolt11.h"
 #include "table_audit.h"
-#include "bolt12_text.h"
 
 using namespace lamd;
-
-constexpr int MAX_LANES = 8;
 
 // Wave priority (s_setprio) of the kernels that run UNDER the big table-driven ecmult launches of the other lanes: a front-end / ladder wave
 // that shares a SIMD with three ecmult waves gets the issue port first, so a call's dependent chain of small launches (and its handful of
@@ -43,9 +18,6 @@ __device__ u32 g_prio;
 // Default 13 = front end + scalar preparation + key tables (round 6, profiles/r06_strong_scaling.txt session ac: a 1/8 gossip shard 3.48 against 3.65 ms --
 // the 30 waves of 1 875 node keys' doubling chains no longer wait their turn behind three ladder waves per SIMD -- and the headline loop +0.5 %; rounds 4-5
 // ran with 0: there the mask cost the chained loop 1-9 %, before the front end was fused).
-#ifndef LAMD_PRIO_DEFAULT
-#define LAMD_PRIO_DEFAULT 13
-#endif
 #define LAMD_PRIO(bit)                                     \
   do {                                                     \
     if (g_prio & (bit)) __builtin_amdgcn_s_setprio(3);     \
@@ -119,7 +91,6 @@ __global__ void __launch_bounds__(256) k_keys(size_t n, const u8 *__restrict__ p
 // workloads nearly every cold row is a damaged key (1.25 % of the rows: unique by construction, so never worth a table), and a
 // ladder wave with one live lane costs as much as a full one -- the ladder kernel's VALU work drops from ~2 % of the rows to the
 // few hundred rows under genuinely rare keys.
-__device__ __forceinline__ u32 wave_alloc(u32 *counter, bool pred, u32 weight = 0, u32 *wsum = nullptr);
 __global__ void __launch_bounds__(256) k_keys_cold(size_t n, const u8 *__restrict__ pub, int publen, size_t stride, const u32 *__restrict__ idx,
                                                    const u32 *__restrict__ count, u32 *__restrict__ counter_ok, u32 *__restrict__ idx_ok,
                                                    u32 *__restrict__ qwords, u8 *__restrict__ keyok_row, u8 *__restrict__ out) {
@@ -218,327 +189,6 @@ __global__ void __launch_bounds__(256) k_recover_final(size_t n, u32 *__restrict
   recover_final_thread(tid, T, n, slots, out, pub33);
 }
 
-// ---- gossip: per message, double-SHA256 of the signed tail and expansion into (hash, sig, key) rows
-// ---- check_tx_sig batches: double-SHA256 of caller-built BIP143 preimages (bitcoin/signature.c:120-151 hashes them
-// through libwally) and the sighash-type gate of bitcoin/signature.c:206-211
-// (txsig_hash_one / txsig_tx_hash_one / gossip_expand_one / gossip_reduce_one: verify_core.h -- shared by these kernels and by the host-side latency paths,
-// and compiled for the host by tests/devmath_host.cpp)
-__global__ void __launch_bounds__(256) k_txsig_hash(size_t n, const u8 *__restrict__ pre, const u64 *__restrict__ off,
-                                                    const u8 *__restrict__ sighash_type, const u8 *__restrict__ has_witness,
-                                                    u8 *__restrict__ hash32, u8 *__restrict__ gate) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  gate[i] = txsig_hash_one(pre + off[i], (size_t)(off[i + 1] - off[i]), sighash_type[i], has_witness[i] != 0, hash32 + 32 * i);
-}
-// ---- BIP143 on the device, one (transaction, input) per lane: what bip143_sighash() (verify_core.h: the host's form, byte-wise streaming) computes,
-// laid out for a wavefront.  The streaming form compiled to 72 k instructions (every shs_update site carries its own unrolled compression: 580 KB of code for
-// an instruction cache of 64 KB) with the block buffer in scratch because it is indexed by a run-time byte count: 226 us for the 483 HTLC rows of a
-// commitment_signed, a third of it compressions.  Here each of the four streams of a row (hashPrevouts, hashSequence, hashOutputs, the preimage) is laid
-// out as a padded message in a per-lane LDS buffer -- word j of lane t at w[j * TXH_LANES + t], so a wave's accesses fall into 64 different banks whatever
-// position each lane is at -- and hashed by ONE loop with ONE compression site (the second hash of the double SHA-256 is that loop's last turn).  Bytes
-// from global memory are fetched sixteen at a time so that their latencies overlap.  A row whose streams do not fit the buffer never gets here: txsig_pack
-// hashes it on the host (TXSIG_DEV_MAX_*).
-constexpr int TXH_LANES = 64;
-constexpr u32 TXH_WORDS = 240;                      // per lane: 960 bytes = 15 blocks (61 440 bytes of LDS per work-group)
-constexpr u32 TXH_MAX_STREAM = 4 * TXH_WORDS - 9;   // 0x80 and the 64-bit length must fit behind the message
-__device__ __forceinline__ void txh_put(u32 *w, u32 pos, u32 byte) {  // message byte `pos`; words are big-endian, LDS is little-endian
-  reinterpret_cast<u8 *>(w + (size_t)(pos >> 2) * TXH_LANES)[3 - (pos & 3)] = (u8)byte;
-}
-__device__ __forceinline__ u32 txh_copy(u32 *w, u32 pos, const u8 *__restrict__ p, u32 n) {
-#pragma unroll 1
-  for (u32 k = 0; k < n; k += 16) {
-    u32 b[16];
-#pragma unroll
-    for (u32 j = 0; j < 16; j++) b[j] = p[k + j < n ? k + j : n - 1];  // sixteen loads in flight; the index is clamped, not predicated
-#pragma unroll
-    for (u32 j = 0; j < 16; j++)
-      if (k + j < n) txh_put(w, pos + k + j, b[j]);
-  }
-  return pos + n;
-}
-__device__ __forceinline__ u32 txh_put_be32(u32 *w, u32 pos, u32 v) {
-#pragma unroll
-  for (int k = 0; k < 4; k++) txh_put(w, pos + k, v >> (24 - 8 * k));
-  return pos + 4;
-}
-__device__ __forceinline__ u32 txh_put_le(u32 *w, u32 pos, u64 v, int bytes) {
-  for (int k = 0; k < bytes; k++) txh_put(w, pos + k, (u32)(v >> (8 * k)));
-  return pos + bytes;
-}
-// false: the template is inconsistent (bip143_sighash's cases) or a stream does not fit the buffer; h = SHA256d of the preimage as 8 big-endian words
-__device__ __forceinline__ bool bip143_sighash_lane(u32 *w, const tx_view &t, u32 in_idx, const u8 *__restrict__ script, u32 script_len, u64 amount,
-                                                    u32 sighash_type, u32 h[8]) {
-  if (in_idx >= t.n_in) return false;
-  if (t.outputs_len > TXH_MAX_STREAM || (u64)t.n_in * 36 > TXH_MAX_STREAM || (u64)script_len + 165 > TXH_MAX_STREAM) return false;
-  const bool acp = (sighash_type & 0x80u) != 0;
-  const u32 base = sighash_type & 0x1fu;
-  const bool single = base == 3, none = base == 2;
-  // the outputs must parse; SINGLE needs the boundaries of output [in_idx]
-  size_t at = 0, one_off = 0, one_len = 0;
-  for (u32 k = 0; k < t.n_out; k++) {
-    if (t.outputs_len - at < 8) return false;
-    u64 sl;
-    const size_t l = tx_compact_size(t.outputs + at + 8, t.outputs_len - at - 8, &sl);
-    if (!l || sl > t.outputs_len - at - 8 - l) return false;
-    const size_t len = 8 + l + (size_t)sl;
-    if (k == in_idx) { one_off = at; one_len = len; }
-    at += len;
-  }
-  if (at != t.outputs_len) return false;
-  u32 hp[8], hs[8], ho[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) hp[j] = hs[j] = ho[j] = h[j] = 0;
-#pragma unroll 1
-  for (int ph = 0; ph < 4; ph++) {
-    u32 len = 0;
-    bool run = true;
-    if (ph == 0) {  // hashPrevouts
-      run = !acp;
-      if (run)
-        for (u32 i = 0; i < t.n_in; i++) len = txh_copy(w, len, t.inputs + 40 * (size_t)i, 36);
-    } else if (ph == 1) {  // hashSequence
-      run = !acp && !single && !none;
-      if (run)
-        for (u32 i = 0; i < t.n_in; i++) len = txh_copy(w, len, t.inputs + 40 * (size_t)i + 36, 4);
-    } else if (ph == 2) {  // hashOutputs
-      if (single) {
-        run = in_idx < t.n_out;
-        if (run) len = txh_copy(w, 0, t.outputs + one_off, (u32)one_len);
-      } else if (none) {
-        run = false;
-      } else {
-        len = txh_copy(w, 0, t.outputs, (u32)t.outputs_len);
-      }
-    } else {  // nVersion | hashPrevouts | hashSequence | outpoint | varint script | amount | nSequence | hashOutputs | nLockTime | type
-      len = txh_put_le(w, len, t.version, 4);
-#pragma unroll
-      for (int j = 0; j < 8; j++) len = txh_put_be32(w, len, hp[j]);
-#pragma unroll
-      for (int j = 0; j < 8; j++) len = txh_put_be32(w, len, hs[j]);
-      len = txh_copy(w, len, t.inputs + 40 * (size_t)in_idx, 36);
-      if (script_len < 0xfd) len = txh_put_le(w, len, script_len, 1);
-      else if (script_len <= 0xffff) { len = txh_put_le(w, len, 0xfd, 1); len = txh_put_le(w, len, script_len, 2); }
-      else { len = txh_put_le(w, len, 0xfe, 1); len = txh_put_le(w, len, script_len, 4); }
-      len = txh_copy(w, len, script, script_len);
-      len = txh_put_le(w, len, amount, 8);
-      len = txh_copy(w, len, t.inputs + 40 * (size_t)in_idx + 36, 4);
-#pragma unroll
-      for (int j = 0; j < 8; j++) len = txh_put_be32(w, len, ho[j]);
-      len = txh_put_le(w, len, t.locktime, 4);
-      len = txh_put_le(w, len, sighash_type, 4);
-    }
-    if (!run) continue;
-    // padding: 0x80, zeros to the last two words of a block, the bit length
-    u32 pos = len;
-    txh_put(w, pos++, 0x80u);
-    while (pos & 3) txh_put(w, pos++, 0u);
-    u32 wi = pos >> 2;
-    for (; (wi & 15) != 14; wi++) w[(size_t)wi * TXH_LANES] = 0;
-    w[(size_t)wi * TXH_LANES] = 0;
-    w[(size_t)(wi + 1) * TXH_LANES] = len * 8;
-    const u32 nb = (wi + 2) >> 4;
-    u32 st[8] = LAMD_SHA256_IV;
-#pragma unroll 1
-    for (u32 b = 0; b <= nb; b++) {  // turn nb = the second hash, over the first one's digest
-      u32 x[16];
-      if (b < nb) {
-#pragma unroll
-        for (u32 j = 0; j < 16; j++) x[j] = w[(size_t)(16 * b + j) * TXH_LANES];
-      } else {
-        const u32 iv[8] = LAMD_SHA256_IV;
-#pragma unroll
-        for (int j = 0; j < 8; j++) { x[j] = st[j]; st[j] = iv[j]; }
-        x[8] = 0x80000000u;
-#pragma unroll
-        for (int j = 9; j < 15; j++) x[j] = 0;
-        x[15] = 256;
-      }
-      sha256_compress(st, x);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      if (ph == 0) hp[j] = st[j];
-      else if (ph == 1) hs[j] = st[j];
-      else if (ph == 2) ho[j] = st[j];
-      else h[j] = st[j];
-    }
-  }
-  return true;
-}
-// hash32 must be 4-byte aligned (it is a device allocation of the context)
-__global__ void __launch_bounds__(TXH_LANES) k_txsig_tx_hash(size_t n, const u32 *__restrict__ version, const u32 *__restrict__ locktime,
-                                                             const u8 *__restrict__ inputs40, const u64 *__restrict__ in_off,
-                                                             const u32 *__restrict__ input_num, const u64 *__restrict__ amount,
-                                                             const u8 *__restrict__ outputs, const u64 *__restrict__ out_off,
-                                                             const u32 *__restrict__ n_outputs, const u8 *__restrict__ scripts,
-                                                             const u64 *__restrict__ script_off, const u8 *__restrict__ sighash_type,
-                                                             const u8 *__restrict__ has_witness, const u8 *__restrict__ host_done,
-                                                             const u8 *__restrict__ host_hash, u8 *__restrict__ hash32, u8 *__restrict__ gate) {
-  __shared__ u32 lds[TXH_WORDS * TXH_LANES];
-  const size_t i = (size_t)blockIdx.x * TXH_LANES + threadIdx.x;
-  if (i >= n) return;
-  if (host_done[i]) {  // a row with a long input / output list or script: the host hashed it (txsig_pack) -- one lane would walk 20 KB of outputs for milliseconds
-    for (int b = 0; b < 32; b++) hash32[32 * i + b] = host_hash[32 * i + b];
-    gate[i] = host_done[i] == 1;
-    return;
-  }
-  const u8 t = sighash_type[i];
-  bool pass = t == 1 || (t == 0x83 && has_witness[i]);  // the gate of bitcoin/signature.c:206-211 (txsig_tx_hash_one)
-  u32 h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (pass) {
-    tx_view tv;
-    tv.version = version[i];
-    tv.locktime = locktime[i];
-    tv.inputs = inputs40 + 40 * in_off[i];
-    tv.n_in = (u32)(in_off[i + 1] - in_off[i]);
-    tv.outputs = outputs + out_off[i];
-    tv.outputs_len = (size_t)(out_off[i + 1] - out_off[i]);
-    tv.n_out = n_outputs[i];
-    const u64 sl = script_off[i + 1] - script_off[i];
-    pass = sl <= TXH_MAX_STREAM && bip143_sighash_lane(lds + threadIdx.x, tv, input_num[i], scripts + script_off[i], (u32)sl, amount[i], t, h);
-  }
-  u32 *out = reinterpret_cast<u32 *>(hash32) + 8 * i;
-#pragma unroll
-  for (int j = 0; j < 8; j++) out[j] = pass ? __builtin_bswap32(h[j]) : 0u;
-  gate[i] = pass;
-}
-// ---- BOLT #12: merkle root + tagged signature hash of one TLV stream per lane (bolt12.h); valid[i] = the stream obeys the TLV rules
-__global__ void __launch_bounds__(64) k_bolt12_hash(size_t n, const u8 *__restrict__ tlvs, const u64 *__restrict__ off, bolt12_mids mids,
-                                                    u8 *__restrict__ root32, u8 *__restrict__ msg32, u8 *__restrict__ valid) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  u8 root[32], msg[32];
-  for (int b = 0; b < 32; b++) root[b] = msg[b] = 0;
-  const bool ok = bolt12_merkle_root(tlvs + off[i], (size_t)(off[i + 1] - off[i]), mids, root);
-  if (ok) bolt12_sighash(mids, root, msg);
-  valid[i] = ok;
-  for (int b = 0; b < 32; b++) { if (root32) root32[32 * i + b] = root[b]; msg32[32 * i + b] = msg[b]; }
-}
-__global__ void __launch_bounds__(256) k_apply_gate(size_t n, const u8 *__restrict__ gate, u8 *__restrict__ ok) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && !gate[i]) ok[i] = 0;
-}
-
-// ---- text front ends, one string per lane (bolt11.h): the columns the recovery and verification launches behind them take.  A row belongs to the
-// recovery batch (no `n` key) or to the verification batch (`n` key) only with status 0 so far; for every other row the batch gets what its early
-// reject removes -- recovery id 0xFF, a zero signature -- so both batches run over all n rows and nothing is compacted.  A row without an `n` key
-// carries the generator as its key: the key-parse kernel and the verification batch see a valid point.
-__device__ __constant__ static const u8 TEXT_DUMMY_KEY[33] = {0x02, 0x79, 0xBE, 0x66, 0x7E, 0xF9, 0xDC, 0xBB, 0xAC, 0x55, 0xA0, 0x62, 0x95, 0xCE, 0x87, 0x0B, 0x07,
-                                                              0x02, 0x9B, 0xFC, 0xDB, 0x2D, 0xCE, 0x28, 0xD9, 0x59, 0xF2, 0x81, 0x5B, 0x16, 0xF8, 0x17, 0x98};
-__global__ void __launch_bounds__(64) k_bolt11_front(size_t n, const u8 *__restrict__ strs, const u64 *__restrict__ off, int8_t *__restrict__ pre,
-                                                     u8 *__restrict__ hash32, u8 *__restrict__ sig64, u8 *__restrict__ recid_rec, u8 *__restrict__ sig_ver,
-                                                     u8 *__restrict__ key33, u8 *__restrict__ have_n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  u8 recid, hn;
-  const int st = bolt11_front_one(strs + off[i], (size_t)(off[i + 1] - off[i]), hash32 + 32 * i, sig64 + 64 * i, &recid, key33 + 33 * i, &hn);
-  pre[i] = (int8_t)st;
-  have_n[i] = hn;
-  recid_rec[i] = st == LAMD_B11_OK && !hn ? recid : 0xFF;
-  const bool ver = st == LAMD_B11_OK && hn;
-  for (int b = 0; b < 64; b++) sig_ver[64 * i + b] = ver ? sig64[64 * i + b] : 0;
-  if (!hn)
-    for (int b = 0; b < 33; b++) key33[33 * i + b] = TEXT_DUMMY_KEY[b];
-}
-__global__ void __launch_bounds__(64) k_checkmessage_front(size_t n, const u8 *__restrict__ msgs, const u64 *__restrict__ moff, const u8 *__restrict__ zb,
-                                                           const u64 *__restrict__ zoff, int8_t *__restrict__ pre, u8 *__restrict__ hash32,
-                                                           u8 *__restrict__ sig64, u8 *__restrict__ recid_rec) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  u8 recid;
-  const int st = checkmessage_front_one(msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), zb + zoff[i], (size_t)(zoff[i + 1] - zoff[i]), hash32 + 32 * i,
-                                        sig64 + 64 * i, &recid);
-  pre[i] = (int8_t)st;
-  recid_rec[i] = st == LAMD_MSG_OK ? recid : 0xFF;
-}
-// status and key of a row from what the stages left.  have_n == nullptr (checkmessage): no row has a key of its own.  With one: an `n` key that is
-// no point is MALFORMED, in front of what the signature bytes say (the reference parses the key while it walks the fields), and takes the
-// row's hash with it.
-__global__ void __launch_bounds__(256) k_text_merge(size_t n, const int8_t *__restrict__ pre, u8 *__restrict__ have_n, const u8 *__restrict__ keyok,
-                                                    const u8 *__restrict__ ok_ver, const u8 *__restrict__ ok_rec, const u8 *__restrict__ pub_rec,
-                                                    const u8 *__restrict__ key33, u8 *__restrict__ hash32, int no_key, int8_t *__restrict__ status,
-                                                    u8 *__restrict__ node_id33) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const bool hn = have_n && have_n[i];
-  int st = pre[i];
-  if (hn && !keyok[i] && (st == LAMD_B11_OK || st == LAMD_B11_BAD_RECID || st == LAMD_B11_SIG_RANGE)) {
-    st = LAMD_B11_MALFORMED;
-    have_n[i] = 0;
-    for (int b = 0; b < 32; b++) hash32[32 * i + b] = 0;
-  }
-  if (st == 0) {
-    if (hn) st = ok_ver[i] == 1 ? 0 : LAMD_B11_BAD_SIGNATURE;
-    else st = ok_rec[i] == 1 ? 0 : no_key;
-  }
-  status[i] = (int8_t)st;
-  const u8 *src = hn ? key33 + 33 * i : pub_rec + 33 * i;
-  for (int b = 0; b < 33; b++) node_id33[33 * i + b] = st == 0 ? src[b] : 0;
-}
-
-// ---- BOLT #12 from its text, one string per lane (bolt12_text.h).  Row i decodes into scratch[off[i] .. off[i+1]): a string never decodes to more bytes
-// than it has, so the rows cannot overlap.  Only a row with status 0 so far and a key of its own (an invoice request, an invoice) belongs to the BIP-340
-// batch; every other row gets what the batch's early reject removes -- a zero signature under the generator's x -- so the batch runs over all n rows.
-// key33 keeps a present key whatever the status behind it (-5, -7, 0), for the key-parse kernel's validity byte; without one it holds the generator.
-__global__ void __launch_bounds__(64) k_bolt12_text_front(size_t n, const u8 *__restrict__ strs, const u64 *__restrict__ off, u8 *__restrict__ scratch,
-                                                          bolt12_text_mids mids, int8_t *__restrict__ pre, u8 *__restrict__ kind, u8 *__restrict__ have_key,
-                                                          u8 *__restrict__ key33, u8 *__restrict__ xonly, u8 *__restrict__ sig64, u8 *__restrict__ hash32,
-                                                          u8 *__restrict__ offer_id, u8 *__restrict__ invreq_id) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const size_t len = (size_t)(off[i + 1] - off[i]);
-  size_t dlen;
-  u8 kd, hk;
-  const int st = bolt12_text_front_one(strs + off[i], len, scratch + off[i], len, &dlen, mids, &kd, key33 + 33 * i, &hk, sig64 + 64 * i, hash32 + 32 * i,
-                                       offer_id + 32 * i, invreq_id + 32 * i);
-  pre[i] = (int8_t)st;
-  kind[i] = kd;
-  have_key[i] = hk;
-  const bool ver = st == LAMD_B12_OK && kd != LAMD_B12_KIND_OFFER;
-  for (int b = 0; b < 32; b++) xonly[32 * i + b] = ver ? key33[33 * i + 1 + b] : TEXT_DUMMY_KEY[1 + b];
-  if (!hk)
-    for (int b = 0; b < 33; b++) key33[33 * i + b] = TEXT_DUMMY_KEY[b];
-}
-// status, signer and ids of a row from what the stages left.  A present key that is no curve point is MALFORMED (fromwire_pubkey fails inside
-// fromwire_tlv), ahead of what the ranges, field 240 and the signature say, and takes the row's hash with it.
-__global__ void __launch_bounds__(256) k_bolt12_text_merge(size_t n, const int8_t *__restrict__ pre, const u8 *__restrict__ kind, const u8 *__restrict__ have_key,
-                                                           const u8 *__restrict__ keyok, const u8 *__restrict__ ok_ver, const u8 *__restrict__ key33,
-                                                           u8 *__restrict__ hash32, u8 *__restrict__ offer_id, u8 *__restrict__ invreq_id,
-                                                           int8_t *__restrict__ status, u8 *__restrict__ signer33) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int st = pre[i];
-  const bool own_key = kind[i] == LAMD_B12_KIND_INVREQ || kind[i] == LAMD_B12_KIND_INVOICE;
-  if (have_key[i] && !keyok[i] && (st == LAMD_B12_OK || st == LAMD_B12_OUT_OF_RANGE || st == LAMD_B12_NO_SIGNATURE)) {
-    st = LAMD_B12_MALFORMED;
-    for (int b = 0; b < 32; b++) hash32[32 * i + b] = 0;
-  }
-  if (st == LAMD_B12_OK && own_key) st = ok_ver[i] == 1 ? LAMD_B12_OK : LAMD_B12_BAD_SIGNATURE;
-  status[i] = (int8_t)st;
-  if (st != LAMD_B12_OK)
-    for (int b = 0; b < 32; b++) offer_id[32 * i + b] = invreq_id[32 * i + b] = 0;
-  for (int b = 0; b < 33; b++) signer33[33 * i + b] = st == LAMD_B12_OK && own_key ? key33[33 * i + b] : 0;
-}
-
-// ---- fee grind (verify_core.h "fee grind"): one thread prepares, one thread per candidate feerate
-__global__ void __launch_bounds__(64) k_grind_setup(const u8 *__restrict__ sig64, const u8 *__restrict__ pub33,
-                                                    const u8 *__restrict__ pre, u32 lead_blocks, u32 *__restrict__ slot,
-                                                    const u32 *__restrict__ gtable, grind_setup *__restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  grind_setup g;
-  grind_prepare(&g, sig64, pub33, pre, lead_blocks, slot, gtable);
-  *out = g;
-}
-// candidate c = feerate min_rate + c; *best = the smallest matching c (0xFFFFFFFF: none)
-__global__ void __launch_bounds__(256) k_grind(u32 ncand, u32 min_rate, u64 weight, u64 input_sat, const u8 *__restrict__ tail,
-                                               u32 tail_len, u32 lead_bytes, const u8 *__restrict__ outputs, u32 outputs_len,
-                                               const grind_setup *__restrict__ setup, const u32 *__restrict__ gtable,
-                                               u32 *__restrict__ best) {
-  const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= ncand || !setup->valid) return;
-  if (grind_candidate(c, min_rate, weight, input_sat, tail, tail_len, lead_bytes, outputs, outputs_len, *setup, gtable)) atomicMin(best, c);
-}
-
 // rowbase[i] = index of message i's first signature row; malformed[i] set here for framing errors
 // message i = msgs[off[i], off[i + 1]) -- or, with `len` (the spans form: lamd_sigcheck_gossip_spans_device), msgs[off[i], off[i] + len[i]): the messages of a
 // call need not lie back to back, nor in order
@@ -562,197 +212,6 @@ __global__ void __launch_bounds__(256) k_gossip_reduce(size_t n, const u8 *__res
   verdict[i] = (int8_t)gossip_reduce_one(rowbase[i + 1] - row, ok + row, keyok + row, malformed[i]);
 }
 
-// ---- gossip_store audit (lamd_gossip_store_audit; per-record logic in store_audit.h).  One lane per record throughout.
-// k_store_crc: the block builds the slicing tables in LDS (thread t computes entry t of table 0 from the bitwise definition; every further
-// table reads table 0 only), then each lane checksums its record -- bytes until the pointer is 4-aligned, 32-bit loads, tail bytes -- and
-// classifies it.  A lane's cost is its record's length: gossip records are 130-450 bytes, the 65 535-byte maximum is correct, not fast.
-template <int WAYS>
-__global__ void __launch_bounds__(256) k_store_crc(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                   int8_t *__restrict__ pre) {
-  __shared__ u32 T[WAYS * 256];
-  const u32 t = threadIdx.x;
-  u32 v = store_crc_t0(t);
-  T[t] = v;
-  __syncthreads();
-  for (int k = 1; k < WAYS; k++) {
-    v = (v >> 8) ^ T[v & 0xff];
-    T[256 * k + t] = v;
-  }
-  __syncthreads();
-  const u32 i = blockIdx.x * 256 + t;
-  if (i < n) pre[i] = (int8_t)store_precheck_one<WAYS>(T, store, store_len, rec_off[i]);
-}
-// keys / vals: (1 << bits) + 1 slots, preset to all-ones bytes (STORE_EMPTY_KEY / STORE_NONE)
-__global__ void __launch_bounds__(256) k_store_index(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                     u64 *keys, u32 *vals, u32 bits) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) store_index_one(store, store_len, rec_off[i], i, keys, vals, bits);
-}
-// sel[i] = the record's row in the signature selection (STORE_NONE: it has none): a channel_update's signer goes to ids33 + 33 * sel[i]
-__global__ void __launch_bounds__(256) k_store_signers(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                       const u32 *__restrict__ sel, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                       u32 bits, u8 *__restrict__ ids33, u8 *__restrict__ aux) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const u32 j = sel[i];
-  aux[i] = (u8)store_signer_one(store, store_len, rec_off, i, keys, vals, bits, j != STORE_NONE ? ids33 + 33 * (size_t)j : nullptr);
-}
-__global__ void __launch_bounds__(256) k_store_verdict(u32 n, const int8_t *__restrict__ pre, const u32 *__restrict__ sel,
-                                                       const int8_t *__restrict__ sigv, const u8 *__restrict__ aux, int8_t *__restrict__ verdict) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const u32 j = sel[i];
-  verdict[i] = (int8_t)store_merge_one(pre[i], j != STORE_NONE, j != STORE_NONE ? sigv[j] : 0, aux[i]);
-}
-
-// ---- gossip_store repair (lamd_gossip_store_repair; per-record and per-word logic in store_repair.h), behind k_store_verdict on the same stream.
-// k_store_keep_chan: the live channel_announcements -- reason and size, and the two node ids of each kept one into the node table
-// (nkeys / nvals: 1 << nbits slots, preset to all-ones bytes).  k_store_keep_rest: every other record (it reads the announcements' reasons,
-// so it is a launch of its own); lane n writes the closing size 0, so that the scan ends with the sum.
-__global__ void __launch_bounds__(256) k_store_keep_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                         const int8_t *__restrict__ verdict, u64 *nkeys, u32 *nvals, u32 nbits, u8 *__restrict__ reason,
-                                                         u32 *__restrict__ size) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !store_is_live_cann(store, store_len, rec_off[i])) return;
-  u32 sz;
-  u64 idoff = 0;
-  const u32 r = store_keep_cann(store, store_len, rec_off, verdict, n, i, &sz, &idoff);
-  reason[i] = (u8)r;
-  size[i] = sz;
-  if (r == STORE_DROP_KEPT) {
-    store_node_insert(store, nkeys, nvals, nbits, idoff, i);
-    store_node_insert(store, nkeys, nvals, nbits, idoff + 33, i);
-  }
-}
-__global__ void __launch_bounds__(256) k_store_keep_rest(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                         const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                         u32 bits, const u64 *__restrict__ nkeys, const u32 *__restrict__ nvals, u32 nbits, u8 *reason,
-                                                         u32 *__restrict__ size) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i > n) return;
-  if (i == n) { size[n] = 0; return; }
-  if (store_is_live_cann(store, store_len, rec_off[i])) return;
-  u32 sz;
-  reason[i] = (u8)store_keep_other(store, store_len, rec_off, verdict, n, i, keys, vals, bits, nkeys, nvals, nbits, reason, &sz);
-  size[i] = sz;
-}
-// ---- the keep stages of the latest-wins repair (lamd_gossip_store_repair_latest; per-record logic in store_latest.h) in place of the two
-// kernels above.  Each reads what the one before it wrote with atomics (update slots and dying marks -> announcements and node table ->
-// node slots -> the rest), so each is a launch of its own: no workgroup waits for another.  latest: 2 * n slots, nlatest: 1 << nbits slots,
-// dying: n bytes, all preset to 0; nkeys / nvals as above.  Lane n of k_store_latest_rest writes the closing size 0.
-__global__ void __launch_bounds__(256) k_store_latest_upd(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                          const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                          u32 bits, lamd_store_latest_policy pol, u64 *latest, u8 *dying) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) store_latest_upd_one(store, store_len, rec_off, verdict, i, keys, vals, bits, pol, latest, dying);
-}
-__global__ void __launch_bounds__(256) k_store_latest_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                           const int8_t *__restrict__ verdict, lamd_store_latest_policy pol,
-                                                           const u64 *__restrict__ latest, const u8 *__restrict__ dying, u64 *nkeys, u32 *nvals,
-                                                           u32 nbits, u8 *__restrict__ reason, u32 *__restrict__ size) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || !store_is_live_cann(store, store_len, rec_off[i])) return;
-  u32 sz;
-  u64 idoff = 0;
-  const u32 r = store_latest_cann_one(store, store_len, rec_off, verdict, n, i, pol, latest, dying, &sz, &idoff);
-  reason[i] = (u8)r;
-  size[i] = sz;
-  if (r == STORE_DROP_KEPT) {
-    store_node_insert(store, nkeys, nvals, nbits, idoff, i);
-    store_node_insert(store, nkeys, nvals, nbits, idoff + 33, i);
-  }
-}
-__global__ void __launch_bounds__(256) k_store_latest_node(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                           const int8_t *__restrict__ verdict, const u64 *__restrict__ nkeys,
-                                                           const u32 *__restrict__ nvals, u32 nbits, lamd_store_latest_policy pol, u64 *nlatest) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) store_latest_node_one(store, store_len, rec_off, verdict, i, nkeys, nvals, nbits, pol, nlatest);
-}
-__global__ void __launch_bounds__(256) k_store_latest_rest(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                           const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                           u32 bits, const u64 *__restrict__ nkeys, const u32 *__restrict__ nvals, u32 nbits,
-                                                           lamd_store_latest_policy pol, const u64 *__restrict__ latest,
-                                                           const u64 *__restrict__ nlatest, u8 *reason, u32 *__restrict__ size) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i > n) return;
-  if (i == n) { size[n] = 0; return; }
-  if (store_is_live_cann(store, store_len, rec_off[i])) return;
-  u32 sz;
-  reason[i] = (u8)store_latest_other_one(store, store_len, rec_off, verdict, n, i, keys, vals, bits, nkeys, nvals, nbits, reason, pol, latest, nlatest, &sz);
-  size[i] = sz;
-}
-// The exclusive scan of the sizes, 64-bit, in tiles of STORE_SCAN_TILE = one block: k_store_scan_reduce leaves one sum per tile, the sums are
-// scanned the same way (level by level until one tile holds them), k_store_scan_apply scans inside each tile and adds the tile's base.
-// Separate launches, no workgroup waits for another.  With new_off (the record level) it also writes the records' offsets in the output.
-template <class In>
-__global__ void __launch_bounds__(256) k_store_scan_reduce(u64 n, const In *__restrict__ in, u64 *__restrict__ sums) {
-  __shared__ u64 w[4];
-  const u32 t = threadIdx.x;
-  const u64 i = (u64)blockIdx.x * STORE_SCAN_TILE + t;
-  u64 v = i < n ? (u64)in[i] : 0;
-  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o);
-  if ((t & 63) == 0) w[t >> 6] = v;
-  __syncthreads();
-  if (t == 0) sums[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
-}
-template <class In>
-__global__ void __launch_bounds__(256) k_store_scan_apply(u64 n, const In *in, const u64 *__restrict__ base, u64 *out, u64 n_rec,
-                                                          const u8 *__restrict__ reason, u64 *__restrict__ new_off) {
-  __shared__ u64 s[STORE_SCAN_TILE];
-  const u32 t = threadIdx.x;
-  const u64 i = (u64)blockIdx.x * STORE_SCAN_TILE + t;
-  const u64 v = i < n ? (u64)in[i] : 0;
-  s[t] = v;
-  __syncthreads();
-  for (u32 d = 1; d < STORE_SCAN_TILE; d <<= 1) {
-    const u64 a = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  if (i >= n) return;
-  const u64 x = s[t] - v + (base ? base[blockIdx.x] : 0);
-  out[i] = x;
-  if (new_off && i < n_rec) new_off[i] = reason[i] == STORE_DROP_KEPT ? STORE_REPAIR_HEAD + x : ~(u64)0;
-}
-// k_store_pack: one aligned 32-bit word of the OUTPUT per lane and step, 256 consecutive words per block and step: the stores of a wave
-// are 256 contiguous bytes whatever the records' lengths and alignments, and a lane's time does not depend on any record's length.  A
-// block owns STORE_PACK_WORDS consecutive words; lanes 0 and 1 find the records of its first and last payload byte in the whole scan, the
-// block stages that window of the scan and of the record offsets in LDS and every lane searches there (a window of more than
-// STORE_PACK_STAGE records -- a long run of dropped ones inside the block's bytes -- is searched in global memory instead).  The grid is
-// sized by the upper bound len + 46: blocks behind the output's end leave at once.
-constexpr u32 STORE_PACK_WORDS = 2048;
-__global__ void __launch_bounds__(256) k_store_pack(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                    const u64 *__restrict__ pos, store_head head, u8 *__restrict__ out, u64 out_cap) {
-  __shared__ u32 range[2];
-  __shared__ u32 rel[STORE_PACK_STAGE + 1];
-  __shared__ u64 roff[STORE_PACK_STAGE];
-  const u32 t = threadIdx.x, mis = (u32)((uintptr_t)out & 3);
-  const u64 total = STORE_REPAIR_HEAD + pos[n], lim = out_cap < total ? out_cap : total;
-  const u64 k0 = (u64)blockIdx.x * STORE_PACK_WORDS, k1 = k0 + STORE_PACK_WORDS;
-  if (4 * k0 >= lim + mis) return;
-  if (t < 2) {
-    const u64 bf = 4 * k0 > mis ? 4 * k0 - mis : 0, bl = 4 * k1 - mis < lim ? 4 * k1 - mis : lim;   // the block's bytes: [bf, bl)
-    u32 r = 0;
-    if (bl > STORE_REPAIR_HEAD)
-      r = store_pack_locate(store_pack_global{rec_off, pos}, 0, n - 1, t ? bl - STORE_REPAIR_HEAD - 1 : (bf > STORE_REPAIR_HEAD ? bf - STORE_REPAIR_HEAD : 0));
-    range[t] = r;
-  }
-  __syncthreads();
-  const u32 lo = range[0], hi = range[1];
-  if (hi - lo < STORE_PACK_STAGE) {
-    const u64 base = pos[lo];
-    for (u32 j = t; j <= hi - lo + 1; j += 256) rel[j] = (u32)(pos[lo + j] - base);
-    for (u32 j = t; j <= hi - lo; j += 256) roff[j] = rec_off[lo + j];
-    __syncthreads();
-    const store_pack_staged v{roff, rel, lo, base};
-    for (u64 k = k0 + t; k < k1; k += 256) store_pack_word(store, store_len, v, lo, hi, head, out, lim, mis, k);
-  } else {
-    const store_pack_global v{rec_off, pos};
-    for (u64 k = k0 + t; k < k1; k += 256) store_pack_word(store, store_len, v, lo, hi, head, out, lim, mis, k);
-  }
-}
-
 // (the synthetic-workload signer kernels live in lamd_testgen.hip -> liblightning_amd_testgen.so: test / bench infrastructure,
 // not part of the product library)
 // ---- keyed path kernels (see verify_core.h "Keyed path")
@@ -767,27 +226,6 @@ LAMD_HD u64 key_hash(const u8 *p, int len, u64 seed) {
   }
   return h;
 }
-// Wave-aggregated allocation from a global counter: ONE atomic per wavefront (an uncontended device atomic costs
-// ~10 ns; a million lane-level atomics on one word serialise into >10 ms -- measured).  Every lane of the wave must call
-// it; lanes with pred get consecutive indices.  `weight` (optional) is summed over the pred lanes into *wsum.
-__device__ __forceinline__ u32 wave_alloc(u32 *counter, bool pred, u32 weight, u32 *wsum) {
-  const u64 mask = __ballot(pred);
-  const u32 lane = threadIdx.x & 63u;
-  const u32 prefix = (u32)__popcll(mask & ((1ull << lane) - 1ull));
-  if (wsum) {
-    u32 w = pred ? weight : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o, 64);
-    if (lane == 0 && w) atomicAdd(wsum, w);
-  }
-  u32 base = 0;
-  if (mask == 0) return 0;
-  const int leader = __ffsll((long long)mask) - 1;
-  if ((int)lane == leader) base = atomicAdd(counter, (u32)__popcll(mask));
-  base = __shfl(base, leader, 64);
-  return base + prefix;
-}
-
 // Block-aggregated allocation from up to four global counters at once (round 6), for 256-thread blocks in which EVERY thread calls it: the counters
 // of a call's plan are single words that every wave of the call bumps -- 13 600 waves x 2-4 contended atomics were the 0.3 ms the list builders took
 // for 875 k rows (profiles/r06_shard_timeline_cold.txt).  A block's four waves leave their counts in LDS, four threads do one atomic each for the
@@ -811,130 +249,6 @@ __device__ __forceinline__ void block_alloc4(u32 *const counters[4], const bool 
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < 4; c++) pos[c] = s_base[wave][c] + pre[c];
-}
-
-// ---- gossip_store digest (lamd_gossip_store_digest_build; per-record and per-entry logic in store_digest.h).  One lane per record; each
-// stage reads what the one before wrote with atomics, so each is a launch of its own.  cnt: DIGEST_CNT_* counters, all 0; a wave adds
-// its count with one atomic.  keys / vals: (1 << bits) + 1 slots preset to all-ones bytes; slot: 2 * n words preset to 0.
-enum { DIGEST_CNT_ENTRIES = 0, DIGEST_CNT_CHANNELS = 1, DIGEST_CNT_NO_UPDATE = 2, DIGEST_CNT_NO_CHANNEL = 3, DIGEST_CNT_IN_FRONT = 4, DIGEST_CNT_SHORT = 5, DIGEST_CNTS = 8 };
-__device__ __forceinline__ void wave_count(u32 *counter, bool pred) {
-  const u64 mask = __ballot(pred);
-  if ((threadIdx.x & 63u) == 0 && mask) atomicAdd(counter, (u32)__popcll(mask));
-}
-__global__ void __launch_bounds__(256) k_digest_index(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                      const int8_t *__restrict__ verdict, u64 *keys, u32 *vals, u32 bits) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) store_digest_index_one(store, store_len, rec_off, verdict, i, keys, vals, bits);
-}
-__global__ void __launch_bounds__(256) k_digest_slots(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                      const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                      u32 bits, u32 *slot, u32 *cnt) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  const u32 r = i < n ? store_digest_slot_one(store, store_len, rec_off, verdict, i, keys, vals, bits, slot) : (u32)STORE_DIGEST_UPD_NONE;
-  wave_count(&cnt[DIGEST_CNT_NO_CHANNEL], r == STORE_DIGEST_UPD_NO_CHANNEL);
-  wave_count(&cnt[DIGEST_CNT_IN_FRONT], r == STORE_DIGEST_UPD_IN_FRONT);
-  wave_count(&cnt[DIGEST_CNT_SHORT], r == STORE_DIGEST_UPD_SHORT);
-}
-// the channels with an update, compacted in any order as (scid, announcement index) pairs: pair_key / pair_val hold n pairs preset to
-// all-ones bytes, so that behind the cnt[DIGEST_CNT_ENTRIES] real pairs the largest key stands -- a stable sort of all n pairs leaves the
-// real ones in front, the scid of that value included
-__global__ void __launch_bounds__(256) k_digest_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                     const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                     u32 bits, const u32 *__restrict__ slot, u64 *__restrict__ pair_key, u32 *__restrict__ pair_val, u32 *cnt) {
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  u64 scid = 0;
-  const u32 c = i < n ? store_digest_chan_one(store, store_len, rec_off, verdict, i, keys, vals, bits, slot, &scid) : 0u;
-  const u32 e = wave_alloc(&cnt[DIGEST_CNT_ENTRIES], c == 1, 0, nullptr);
-  if (c == 1 && e < n) {
-    pair_key[e] = scid;
-    pair_val[e] = i;
-  }
-  wave_count(&cnt[DIGEST_CNT_CHANNELS], c != 0);
-  wave_count(&cnt[DIGEST_CNT_NO_UPDATE], c == 2);
-}
-// entry j of the sorted digest, j < cnt[DIGEST_CNT_ENTRIES] (the grid covers n): ann[j] = its announcement.  The CRC tables as in k_store_crc.
-__global__ void __launch_bounds__(256) k_digest_entries(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                        const u32 *__restrict__ slot, const u32 *__restrict__ ann, const u32 *__restrict__ cnt,
-                                                        u32 *__restrict__ ts, u32 *__restrict__ csum, u32 *__restrict__ rec) {
-  __shared__ u32 T[4 * 256];
-  const u32 t = threadIdx.x;
-  u32 v = store_crc_t0(t);
-  T[t] = v;
-  __syncthreads();
-  for (int k = 1; k < 4; k++) {
-    v = (v >> 8) ^ T[v & 0xff];
-    T[256 * k + t] = v;
-  }
-  __syncthreads();
-  const u32 j = blockIdx.x * 256 + t, count = cnt[DIGEST_CNT_ENTRIES] < n ? cnt[DIGEST_CNT_ENTRIES] : n;
-  if (j >= count) return;
-  const u32 a = ann[j];
-  if (a >= n) return;   // (never: the first `count` pairs are real)
-  store_digest_entry_one<4>(T, store, store_len, rec_off, a, slot, ts + 2 * (size_t)j, csum + 2 * (size_t)j, rec + 3 * (size_t)j);
-}
-
-// ---- query_channel_range answers (lamd_channel_range_reply_batch; per-query and per-word logic in store_digest.h).
-// k_range_count: one lane per query runs the searches and the split and leaves the number of its replies and of their bytes.
-__global__ void __launch_bounds__(256) k_range_count(u32 nq, const store_range_query *__restrict__ queries, const u64 *__restrict__ scid, u32 count,
-                                                     u32 *__restrict__ n_msgs, u64 *__restrict__ n_bytes) {
-  const u32 q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nq) return;
-  const store_range_total t = store_range_plan(queries[q], q, scid, count, nullptr, 0);
-  n_msgs[q] = t.msgs;
-  n_bytes[q] = t.bytes;
-}
-// k_range_scan: ONE block; the exclusive scans of both arrays, tile by tile with a carry: msg_first[nq + 1], byte_first[nq + 1]
-__global__ void __launch_bounds__(256) k_range_scan(u32 nq, const u32 *__restrict__ n_msgs, const u64 *__restrict__ n_bytes, u64 *__restrict__ msg_first,
-                                                    u64 *__restrict__ byte_first) {
-  __shared__ u64 sm[256], sb[256];
-  const u32 t = threadIdx.x;
-  u64 cm = 0, cb = 0;
-  for (u32 base = 0; base <= nq; base += 256) {
-    const u32 q = base + t;
-    const u64 vm = q < nq ? (u64)n_msgs[q] : 0, vb = q < nq ? n_bytes[q] : 0;
-    sm[t] = vm;
-    sb[t] = vb;
-    __syncthreads();
-    for (u32 d = 1; d < 256; d <<= 1) {
-      const u64 am = t >= d ? sm[t - d] : 0, ab = t >= d ? sb[t - d] : 0;
-      __syncthreads();
-      sm[t] += am;
-      sb[t] += ab;
-      __syncthreads();
-    }
-    if (q <= nq) {
-      msg_first[q] = cm + sm[t] - vm;
-      byte_first[q] = cb + sb[t] - vb;
-    }
-    cm += sm[255];
-    cb += sb[255];
-    __syncthreads();
-  }
-}
-// k_range_plan: the split again, now writing: the replies of query q are msgs[msg_first[q] ..], as far as they lie below msg_cap, and
-// msg_off[j] their offsets in the output; the last query's lane closes msg_off with the total
-__global__ void __launch_bounds__(256) k_range_plan(u32 nq, const store_range_query *__restrict__ queries, const u64 *__restrict__ scid, u32 count,
-                                                    const u64 *__restrict__ msg_first, const u64 *__restrict__ byte_first, u64 msg_cap,
-                                                    store_range_msg *__restrict__ msgs, u64 *__restrict__ msg_off) {
-  const u32 q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nq) return;
-  const u64 j0 = msg_first[q];
-  if (q == nq - 1 && msg_first[nq] <= msg_cap) msg_off[msg_first[nq]] = byte_first[nq];
-  if (j0 >= msg_cap) return;
-  const u64 room = msg_cap - j0;
-  const store_range_query qu = queries[q];
-  const store_range_total t = store_range_plan(qu, q, scid, count, msgs + j0, room < 0xFFFFFFFFull ? (u32)room : 0xFFFFFFFFu);
-  u64 off = byte_first[q];
-  for (u32 k = 0; k < t.msgs && k < room; k++) {
-    msg_off[j0 + k] = off;
-    off += store_range_msg_bytes(qu, msgs[j0 + k].n);
-  }
-}
-// k_range_encode: one aligned 32-bit word of the output per lane
-__global__ void __launch_bounds__(256) k_range_encode(u64 words, const store_range_msg *__restrict__ msgs, const u64 *__restrict__ msg_off, u32 n_msgs,
-                                                      const store_range_query *__restrict__ queries, store_digest_view d, u8 *__restrict__ out, u64 total) {
-  const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (k < words) store_range_word(msgs, msg_off, n_msgs, queries, d, out, total, (u32)((uintptr_t)out & 3), k);
 }
 
 // Key-table cache.  One entry per distinct public key that has a comb table: the serialised key bytes
@@ -1880,20 +1194,6 @@ __global__ void __launch_bounds__(256) k_schnorr_final_fin(size_t n, u32 *__rest
 //                                        engine
 // =====================================================================================
 
-static constexpr size_t CHUNK_DEFAULT = (size_t)1 << 22;  // signatures per launch sequence (4 GiB of table slots at most; allocated on demand)
-
-struct devbuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-enum { Q_ECDSA33 = 0, Q_ECDSA65 = 1, Q_SCHNORR = 2, Q_KINDS = 3 };
-#ifndef LAMD_QUEUE_SETS
-#define LAMD_QUEUE_SETS 9
-#endif
-constexpr int QUEUE_SETS = LAMD_QUEUE_SETS;  // staging sets of the streaming queue: one open + up to QUEUE_SETS - 1 flushes in flight
-
 // the static G table, one per device and process (lamd_init / lamd_shutdown)
 struct shared_gtable { std::mutex mu; u32 *p = nullptr; int refs = 0; };
 static std::mutex g_gtable_mu;                       // guards the map only: tables of different devices are built side by side (lamd_multi_init)
@@ -1903,188 +1203,7 @@ static shared_gtable &gtable_slot(int device) {
   return g_gtables[device];
 }
 
-struct lamd_ctx {
-  int device = 0;
-  int gtable_device = -1;
-  hipStream_t stream = nullptr;
-  hipDeviceProp_t prop;
-  u32 *gtable = nullptr;
-  std::string err;
-  // per-call workspaces (grown on demand, reused)
-  devbuf recs, qwords, keyok, slots, vbuf;
-  // keyed path: row -> cache entry, de-duplication of the rows the cache did not know, new keys per comb shape (hk[0]: 7 teeth,
-  // hk[1]: 10 teeth -- representative row, cache entry, table slot; parsed key, validity, build scratch), row lists per shape + cold rows
-  devbuf row_ent, kd_table, kd_rep, kd_uid, kd_uniq, kd_count, kd_newent, plan, kt_fin;
-  struct shape_ws { devbuf row, ent, slot, qwords, keyok, scratch; } hk[2];
-  devbuf list7, list10, listcold, listcold_ok;
-  // latency path (k_small_verify): pinned, device-mapped staging for up to SMALL_MAX rows, the verdict bytes and the completion word
-  u8 *h_small = nullptr;
-  u8 *h_tmpl = nullptr;       // pinned: the flattened transaction templates of a lamd_check_commitment_signed / mid-size check_tx_sig call, copied to HBM from here
-  size_t h_tmpl_cap = 0;
-  devbuf small_done;          // block counter of k_small_verify grids (device memory)
-  std::vector<u64> small_missed;   // fingerprints of keys the latency path verified without a table (MISS_SLOTS, 4-way set-associative)
-  u32 prio_mask = LAMD_PRIO_DEFAULT; // LAMD_PRIO: which kernel classes raise their wave priority (g_prio)
-  unsigned spin_us = 2000;         // LAMD_SPIN_US: longest busy-wait of a latency-path call before it blocks in the runtime
-  std::vector<u64> learn_fps;      // the fingerprints that recurred in the call that set force_learn: only these keys get tables (learn_filter)
-  devbuf learn_dev;
-  bool force_learn = false;         // the next small call on this context builds tables for every key the cache misses
-  u32 small_ticket = 0;
-  bool small_kernel = true;   // LAMD_SMALL_KERNEL=0: such calls take the general path
-  u32 *h_plan = nullptr;   // pinned read-back of the last call's plan + cache counters (statistics only: nothing waits for it)
-  // Key-table cache.  The root context owns the shared one (LAMD_CACHE=1, default): entries + index + one table pool per
-  // comb shape, filled by whichever lane meets a key often enough, looked up by every later call.  With LAMD_CACHE=0 every
-  // lane uses its own private instance without an index, reset at the start of each call (tables live for one call).
-  struct key_cache {
-    bool shared = false;
-    u32 cap_ent = 0, cap7 = 0, cap10 = 0, index_mask = 0;
-    devbuf ents, index, pool7, pool10, counters;
-  } cache_store;
-  key_cache *cache = nullptr;       // what this context's calls use (lanes: the root's when shared)
-  lamd_ctx *root = nullptr;         // lanes: the context that owns them
-  int lane_id = 0;                  // 0 = the root context itself, 1.. = lanes
-  u32 call_seq = 0;                 // root: sequence number of the last submitted keyed call
-  u32 pub_seq[MAX_LANES + 1] = {};  // root: per lane (by lane_id), the sequence number of its last publishing call ...
-  hipEvent_t ev_pub[MAX_LANES + 1] = {};   // ... and the event recorded after it
-  u32 vis_seq[MAX_LANES + 1] = {};  // root: per lane, the newest publishing call the host has SEEN complete
-  bool pub_pending[MAX_LANES + 1] = {};
-  int cache_mode = 1;               // LAMD_CACHE
-  size_t cache_keys = (size_t)1 << 20, cache_keys10 = (size_t)1 << 16;   // LAMD_CACHE_KEYS / LAMD_CACHE_KEYS10
-  u32 cache_hwm[3] = {0, 0, 0};     // root: last counters read back (entries, 7-tooth slots, 10-tooth slots)
-  u32 cache_resets = 0;
-  size_t last_hits = 0, last_cold = 0, last_l7 = 0, last_l10 = 0;
-  devbuf keyok_row;
-  hipStream_t stream2 = nullptr;   // scalar prep runs here, concurrently with the key work on `stream`
-  hipStream_t stream3 = nullptr;   // cold rows of a partitioned chunk
-  hipEvent_t ev_fork = nullptr, ev_prep = nullptr, ev_cold = nullptr, ev_keys = nullptr, ev_sigs = nullptr;
-  bool sigs_pending = false;  // lamd_flush sent the signature copy down another stream: the first kernel of the main stream that reads signatures waits for ev_sigs_wait
-  hipEvent_t ev_sigs_wait = nullptr;   // the event that copy is followed by (the lane's own ev_sigs, or the staging set's)
-  // root only: the H2D copies of the flushes, behind nothing but each other (lamd_flush).  Round 5 experiment: SEVERAL such streams, successive flushes taking
-  // turns (LAMD_COPY_STREAMS, default 1: two and three measured SLOWER, 212 / 203 against 218 M/s -- profiles/r05_ab_variants.txt).  On ONE stream the three copies of a flush and the copies of the next flush follow each other with gaps of
-  // 0.1-1 ms (rocprofv3 --memory-copy-trace of the cold streaming loop, profiles/r05_stream_timeline.txt): 3.0 ms of transfers took 3.5-3.9 ms, the
-  // stream was busy 85-90 % of the time and set the loop's pace -- 4.25 ms per flush against the 4.05 ms the kernels need --, every call's front end
-  // started the moment its keys landed and only one table-driven ecmult launch was ever in flight.  With two streams the next flush's copies run in
-  // the gaps of the current one's.
-  static constexpr int MAX_COPY_STREAMS = 4;
-  hipStream_t copy_streams[MAX_COPY_STREAMS] = {nullptr, nullptr, nullptr, nullptr};
-  int n_copy_streams = 1;
-  bool copy_one = true;         // LAMD_COPY_ONE=0: a full staging set still goes down as three copies
-  int copy_events = 0;          // LAMD_COPY_EVENTS: events a flush records between / behind its three copies (3: keys | signatures | hashes, 2: keys | rest, 1: all; 0: by load)
-  unsigned copy_turn = 0;
-  bool use_copy_stream = true;         // LAMD_COPY_STREAM=0: a flush's copies go down its lane's prep stream (the round-2 form)
-  int keyed_mode = -1;           // -1 auto, 0 never, 1 whenever keys repeat at all (LAMD_KEYED)
-  size_t keyed_min_rows = 8192;  // below this a batch is latency-bound: per-signature ladder
-  bool early_cold = true;         // LAMD_EARLY_COLD=0: the cold rows' list is made by k_partition, after the table kernels (rounds 1-5)
-  bool fused_front = true;        // LAMD_FUSED_FRONT=0: the front end of a keyed call as the 19 launches + 5 fills of round 2 (see k_call_init)
-  bool kc_tree = false;           // LAMD_KC_TREE=1: key tables by the affine tree builder (k_kc_tree_both) instead of the Gray-code chains (k_kc_finish_both); read on the root context
-  bool small_fused = true;        // LAMD_SMALL_FUSED=0: small batches take the partitioning path even with a cache
-  bool last_small_fused = false;  // the previous small batch of this lane ran k_ecmult_small (its plan holds P_DENSE)
-  size_t last_small_n = 0;
-  double keyed_min_uses = 6.0;   // average signatures per distinct key that pays for a (comb) table
-  double keyed_dense_uses = 48.0;  // ... and for the 10-tooth comb (512 entries per key)
-  int keyed_teeth = 0;             // 0 = choose by re-use, 7 or 10 = force that comb (LAMD_KEYED_TEETH)
-  int last_mode = 0;
-  size_t last_n = 0;
-  bool last_keyed_call = false;
-  devbuf in_a, in_b, in_c, out;       // staging for the host-buffer API
-  devbuf g_msgs, g_off, g_ids, g_rowbase, g_hash, g_sig, g_pub, g_malformed, g_ok, g_verdict;
-  devbuf st_img, st_host, st_ids, st_tab, st_out;   // gossip_store audit: image, the host walk's arrays, signers, scid index, per-record bytes
-  hipEvent_t ev_store[6] = {};                      // ... and its stage boundaries (created when a timed audit first runs)
-  devbuf st_rep, st_pack;                           // gossip_store repair: reasons, sizes, offsets, block sums, node table; the output image
-  hipEvent_t ev_rep[4] = {};                        // ... and its stage boundaries
-  devbuf st_dig, st_rng, st_rng_out;                // digest build: its tables and the sort's workspace; range replies: plan arrays, the messages
-  hipEvent_t ev_dig[6] = {};                        // ... and the stage boundaries of either call
-  devbuf tx_cols;                                   // text front ends (lamd_bolt11_check_batch, lamd_checkmessage_batch): the per-row columns
-  hipEvent_t ev_text[3] = {};                       // ... in front of the front-end kernel, behind it, behind the merge (created when a timed call first runs)
-  double text_ms[2] = {0, 0};                       // ... and what they measured last: front end, curve work + merge
-  // timing
-  bool timing = false;
-  bool ev_recorded = false;
-  int ecmult_waves = 3;
-  bool pairs = false;              // LAMD_PAIRS=1 (experiment, parity-green, measured slower: DESIGN.md 4): the table-driven ecmult of a large call pairs first (k_ecmult_keyed_pairs)
-                                   // instead of one mixed addition per table entry (k_ecmult_keyed<false>)
-  bool group_rows = true;          // LAMD_GROUP=0: the row lists of a large call stay in arrival order (no k_group_*)
-  devbuf g_cnt, g_base, g_rank, g_touched, g_list7, g_list10;   // k_group_*: histogram / range bases over the cache's entry ids, rank per listed row, touched entries, grouped lists
-  devbuf pairs_ws;                 // parking slots of k_ecmult_keyed_pairs (PAIRS_SLOTS x 48 bytes per resident lane)
-  size_t prep_batch = 16;  // signatures sharing one scalar inversion in the ECDSA prep (LAMD_PREP_BATCH)
-  size_t prep_min_threads = 0;  // LAMD_PREP_MIN_THREADS: fewest prep threads of a large batch (0 = 256 per CU)
-  u64 hash_seed = 0x243F6A8885A308D3ULL;
-  size_t chunk = CHUNK_DEFAULT;  // LAMD_CHUNK_ROWS (tests force small chunks to exercise the splitting)
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  double last_ms[4] = {0, 0, 0, 0};
-  // the dominant kernel alone: an event pair right around every large table-driven ecmult launch while timing is on (the
-  // start event sits AFTER the waits for the prep / cold streams, so the interval is the launch itself, as rocprofv3 sees it);
-  // read and summed per mode (ECDSA / BIP-340) by lamd_synchronize(), reset by lamd_set_timing()
-  static const int MARK_SLOTS = 16;
-  hipEvent_t ev_mark[MARK_SLOTS][MAX_LANES + 1] = {};  // lamd_results_mark(): one event per lane stream (+ the context's own)
-  bool mark_set[MARK_SLOTS] = {};
-  int mark_only[MARK_SLOTS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};  // lamd_results_mark_last(): the one lane whose event the slot holds (-1: every lane's)
-  static const int KEV = 64;
-  hipEvent_t kev[KEV][2] = {};
-  int kev_mode[KEV] = {};
-  int kev_n = 0;
-  double keyed_ms_sum[2] = {0, 0};
-  size_t keyed_launches[2] = {0, 0};
-  // streaming queues (pinned host staging): QUEUE_SETS sets, one being filled while up to QUEUE_SETS - 1 flushed ones are
-  // in flight (each on the lane picked at its flush), collected oldest first
-  struct queue {
-    // ONE pinned block per (set, kind), laid out for `cap` rows: keys | signatures | hashes (the order a flush sends them); h_c / h_b / h_a point
-    // into it.  A flush that fills the set exactly (n == cap: a producer that reserves its batch in one go) crosses the bus as ONE copy.
-    u8 *h_blk = nullptr;
-    u8 *h_a = nullptr, *h_b = nullptr, *h_c = nullptr, *h_ok = nullptr;  // hash/msg, sig, key (inside h_blk); verdicts (own block)
-    size_t cap = 0, n = 0;
-    static size_t key_bytes_padded(size_t cap, size_t keybytes) { return (cap * keybytes + 63) & ~(size_t)63; }
-    static size_t blk_bytes(size_t cap, size_t keybytes) { return key_bytes_padded(cap, keybytes) + cap * 96; }
-    struct span { size_t row0; u32 ticket0; size_t count; };
-    std::vector<span> tickets;  // rows [row0, row0 + count) of this queue return as verdicts [ticket0, ...) of the staging set
-    // rows that were queued IN PLACE (lamd_queue_*_batch_inplace): they have a row range in the set and in its device twin like any other, but
-    // their bytes stay in the caller's (registered) memory and cross the bus from there -- no host copy at all.  Ordered by row0, disjoint.
-    struct foreign_span { size_t row0, count; const u8 *a, *b, *c; };
-    std::vector<foreign_span> foreign;
-    devbuf d_blk, d_ok;   // the device twin of h_blk (same layout), the verdicts
-    hipEvent_t ev_keys = nullptr, ev_sigs = nullptr, ev_all = nullptr;  // behind the three H2D copies of a flush on the copy stream
-    bool small_flush = false;   // this flush ran as ONE k_small_verify launch over the staging rows themselves (h_ok + cap: the rows' shapes)
-  };
-  struct queue_set {
-    queue q[Q_KINDS];
-    hipEvent_t done = nullptr;
-    size_t rows = 0;  // triples queued into this set so far = the next ticket
-  } qs[QUEUE_SETS];
-  int q_open = 0;                 // the set being filled, -1 when every set is in flight
-  int q_fifo[QUEUE_SETS] = {0};   // flushed sets, oldest first
-  int q_inflight = 0;
-  size_t last_flush_inplace_rows = 0;   // rows the last successful lamd_flush sent from the callers' registered memory (lamd_info)
-  // Lanes: the device-pointer entry points rotate over LAMD_LANES (default 6) complete sub-contexts (own streams and
-  // workspaces, the G table shared), so that the latency-bound front end of one call (key de-duplication, the count
-  // read-back, table building) runs under the VALU-bound ecmult kernels of the calls before it.  A lane's `peer` is the
-  // next lane; the root context (the handle the caller holds) keeps its own stream for staging, queues, generators.
-  lamd_ctx *lane[MAX_LANES] = {};
-  int nlanes = 0;
-  lamd_ctx *peer = nullptr;
-  lamd_ctx *last_lane = nullptr;
-  lamd_ctx *last_chunk_lane = nullptr;  // where the last chunk of this lane's last call ran (itself or its peer)
-  bool is_lane = false;
-  int next_lane = 0;
-  hipEvent_t ev_lane = nullptr, ev_join = nullptr;
-  // root: the large table-driven ecmult launches of successive calls run one after the other (LAMD_ECMULT_CHAIN, see ecmult_stage)
-  hipEvent_t ev_ecm[MAX_LANES + 1] = {};
-  int ecm_last = -1;
-  int ecm_chain = 0;
-  size_t ecm_chain_min = 65536;
-  u32 ecm_tail = 131072;             // LAMD_ECMULT_TAIL: work items of the low-priority second part (LAMD_ECMULT_CHAIN=2)
-  hipStream_t stream_lo = nullptr;   // lanes, LAMD_ECMULT_CHAIN=2: lowest-priority stream of that second part
-  hipEvent_t ev_lo_go = nullptr, ev_lo_done = nullptr;
-};
-
-#define HIPCHK(ctx, call)                                                                           \
-  do {                                                                                              \
-    hipError_t e_ = (call);                                                                         \
-    if (e_ != hipSuccess) {                                                                         \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                               \
-      return LAMD_ERR_HIP;                                                                          \
-    }                                                                                               \
-  } while (0)
-
-static int ensure(lamd_ctx *ctx, devbuf *b, size_t bytes) {
+int ensure(lamd_ctx *ctx, devbuf *b, size_t bytes) {
   if (bytes <= b->cap) return LAMD_OK;
   // growing a workspace: an earlier, still running call of this context may be using the old one.  Do not rely on
   // hipFree() waiting for other streams -- drain the device first (rare: sizes settle after the first calls).
@@ -2106,14 +1225,7 @@ static int ensure(lamd_ctx *ctx, devbuf *b, size_t bytes) {
   b->cap = want;
   return LAMD_OK;
 }
-static void release(devbuf *b) {
-  if (b->p) (void)hipFree(b->p);
-  b->p = nullptr;
-  b->cap = 0;
-}
 
-
-static inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 // the complete-formula kernels only see rows the bare formulas flagged (crafted scalars): a few blocks walk the list -- unless the
 // lane's previous call reported many such rows (somebody is crafting them): then the launch covers the batch
 static unsigned careful_grid(const lamd_ctx *ctx, size_t n) {
@@ -2143,7 +1255,6 @@ extern "C" const char *lamd_last_error(const lamd_ctx *ctx) { return ctx ? ctx->
 static int init_known_answers(lamd_ctx *ctx);
 static int cache_alloc(lamd_ctx *owner, lamd_ctx::key_cache *kc, size_t keys7, size_t keys10, bool shared);
 static int cache_reset(lamd_ctx *root);
-static int cache_maybe_reset(lamd_ctx *root);
 
 static int create_streams(lamd_ctx *ctx) {
   HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -2227,7 +1338,7 @@ static int make_lanes(lamd_ctx *root, int count) {
   return LAMD_OK;
 }
 // the lane the next device-pointer call runs on, ordered after whatever is already queued on the context's own stream
-static int pick_lane(lamd_ctx *root, lamd_ctx **out) {
+int pick_lane(lamd_ctx *root, lamd_ctx **out) {
   *out = root;
   const int rcc = cache_maybe_reset(root);
   if (rcc != LAMD_OK) return rcc;
@@ -2359,41 +1470,19 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
   for (hipStream_t cs : ctx->copy_streams)
     if (cs) (void)hipStreamSynchronize(cs);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (devbuf *b : {&ctx->row_ent, &ctx->kd_table, &ctx->kd_rep, &ctx->kd_uid, &ctx->kd_uniq, &ctx->kd_count, &ctx->kd_newent, &ctx->plan,
-                    &ctx->kt_fin, &ctx->list7,
-                    &ctx->list10, &ctx->listcold, &ctx->listcold_ok, &ctx->keyok_row, &ctx->pairs_ws, &ctx->g_cnt, &ctx->g_base, &ctx->g_rank, &ctx->g_touched, &ctx->g_list7, &ctx->g_list10, &ctx->cache_store.ents, &ctx->cache_store.index, &ctx->cache_store.pool7,
-                    &ctx->cache_store.pool10, &ctx->cache_store.counters})
-    release(b);
-  for (auto &w : ctx->hk)
-    for (devbuf *b : {&w.row, &w.ent, &w.slot, &w.qwords, &w.keyok, &w.scratch}) release(b);
   for (auto &e : ctx->ev_pub)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
   if (ctx->stream3 && ctx->stream3 != ctx->stream2) { (void)hipStreamSynchronize(ctx->stream3); (void)hipStreamDestroy(ctx->stream3); }
-  if (ctx->ev_cold) (void)hipEventDestroy(ctx->ev_cold);
-  if (ctx->ev_keys) (void)hipEventDestroy(ctx->ev_keys);
-  if (ctx->ev_sigs) (void)hipEventDestroy(ctx->ev_sigs);
-  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-  if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
-  for (devbuf *b : {&ctx->small_done, &ctx->recs, &ctx->qwords, &ctx->keyok, &ctx->slots, &ctx->vbuf, &ctx->in_a, &ctx->in_b, &ctx->in_c, &ctx->out,
-                    &ctx->g_msgs, &ctx->g_off, &ctx->g_ids, &ctx->g_rowbase, &ctx->g_hash, &ctx->g_sig, &ctx->g_pub,
-                    &ctx->g_malformed, &ctx->g_ok, &ctx->g_verdict, &ctx->st_img, &ctx->st_host, &ctx->st_ids, &ctx->st_tab, &ctx->st_out, &ctx->st_rep,
-                    &ctx->st_pack, &ctx->st_dig, &ctx->st_rng, &ctx->st_rng_out, &ctx->tx_cols})
-    release(b);
-  for (auto &e : ctx->ev_dig)
+  for (hipEvent_t e : {ctx->ev_cold, ctx->ev_keys, ctx->ev_sigs, ctx->ev_fork, ctx->ev_prep})
     if (e) (void)hipEventDestroy(e);
-  for (auto &e : ctx->ev_text)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : ctx->ev_store)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : ctx->ev_rep)
-    if (e) (void)hipEventDestroy(e);
+  ctx->store.destroy_events();
+  ctx->text.destroy_events();
   for (auto &qs : ctx->qs) {
     for (auto &q : qs.q) {
       q.h_a = q.h_b = q.h_c = nullptr;
       for (u8 **h : {&q.h_blk, &q.h_ok})
         if (*h) (void)hipHostFree(*h);
-      for (devbuf *b : {&q.d_blk, &q.d_ok}) release(b);
       for (hipEvent_t e : {q.ev_keys, q.ev_sigs, q.ev_all})
         if (e) (void)hipEventDestroy(e);
     }
@@ -2414,12 +1503,10 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
   }
   if (ctx->h_plan) (void)hipHostFree(ctx->h_plan);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  if (ctx->h_tmpl) (void)hipHostFree(ctx->h_tmpl);
+  if (ctx->tmpl.h) (void)hipHostFree(ctx->tmpl.h);
   if (ctx->stream_lo) { (void)hipStreamSynchronize(ctx->stream_lo); (void)hipStreamDestroy(ctx->stream_lo); }
-  for (hipEvent_t e : {ctx->ev_lo_go, ctx->ev_lo_done})
+  for (hipEvent_t e : {ctx->ev_lo_go, ctx->ev_lo_done, ctx->ev_lane, ctx->ev_join})
     if (e) (void)hipEventDestroy(e);
-  if (ctx->ev_lane) (void)hipEventDestroy(ctx->ev_lane);
-  if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   for (auto &e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   for (auto &pair : ctx->kev)
@@ -2429,7 +1516,7 @@ extern "C" void lamd_shutdown(lamd_ctx *ctx) {
     for (auto &e : slot)
       if (e) (void)hipEventDestroy(e);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;   // every workspace frees itself here (devbuf): the streams have drained and the context's device is current
 }
 
 extern "C" void *lamd_stream(lamd_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
@@ -2591,7 +1678,7 @@ static int get_info_of(lamd_ctx *ctx, lamd_info *info) {
   info->hw_queues_env = hw_queues_from_env();
   info->queue_sets = QUEUE_SETS;
   info->last_flush_inplace_rows = root->last_flush_inplace_rows;
-  for (int i = 0; i < 2; i++) info->last_text_ms[i] = root->text_ms[i];
+  for (int i = 0; i < 2; i++) info->last_text_ms[i] = root->text.ms[i];
   for (int i = 0; i < 4; i++) info->last_kernel_ms[i] = ctx->last_ms[i];
   for (int i = 0; i < 2; i++) {
     info->keyed_ecmult_ms_sum[i] = self->keyed_ms_sum[i];
@@ -3166,7 +2253,7 @@ static int run_chunk(lamd_ctx *ctx, int mode, size_t n, const u8 *d_a, const u8 
 }
 
 // the shared cache is bounded: when the last fill level read back nears a capacity, drain the device and start over
-static int cache_maybe_reset(lamd_ctx *root) {
+int cache_maybe_reset(lamd_ctx *root) {
   if (root->cache_mode == 0 || !root->cache_store.shared) return LAMD_OK;
   const lamd_ctx::key_cache &kc = root->cache_store;
   u32 hw[3] = {0, 0, 0};
@@ -3183,8 +2270,7 @@ static int cache_maybe_reset(lamd_ctx *root) {
   return LAMD_OK;
 }
 
-static int run_device(lamd_ctx *ctx, int mode, size_t n, const u8 *d_a, const u8 *d_sig, const u8 *d_key, int keylen,
-                      size_t keystride, u8 *d_ok, u8 *keyok_out = nullptr) {
+int run_device(lamd_ctx *ctx, int mode, size_t n, const u8 *d_a, const u8 *d_sig, const u8 *d_key, int keylen, size_t keystride, u8 *d_ok, u8 *keyok_out) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!ctx->root) ctx->last_lane = nullptr;  // a call on the context's own streams (host-buffer entry points): lamd_get_info() reports it
   bool forked = false;
@@ -3248,7 +2334,6 @@ extern "C" int lamd_verify_schnorr_batch_device(lamd_ctx *ctx, size_t n, const v
 // n <= SMALL_MAX rows from host memory: one launch of k_small_verify, inputs and verdicts through pinned device-mapped memory, the
 // host waits on the completion word the kernel's last instruction writes
 constexpr size_t SMALL_MAX = 4096;  // rows of a call that takes the one-launch path (a grid of 64-row blocks)
-constexpr size_t TXSIG_HOST_HASH_ROWS = 16;  // check_tx_sig batches up to here hash on the host (one launch); above, on the device (two launches)
 constexpr size_t SMALL_OFF_SIG = SMALL_MAX * 32, SMALL_OFF_KEY = SMALL_OFF_SIG + SMALL_MAX * 64, SMALL_OFF_OUT = SMALL_OFF_KEY + SMALL_MAX * 65 + 64,
                  SMALL_OFF_SHAPES = SMALL_OFF_OUT + SMALL_MAX, SMALL_OFF_FLAG = SMALL_OFF_SHAPES + SMALL_MAX, SMALL_BYTES = SMALL_OFF_FLAG + 64;
 // Keys that the latency path had to take down the ladder are remembered by fingerprint (host side, direct-mapped): the SECOND small
@@ -3301,8 +2386,8 @@ static void small_forget(lamd_ctx *ctx, lamd_ctx *dst, const u8 *key, size_t key
 }
 // d_a32 / d_gate (optional, device memory): the rows' hashes were produced on the device by a kernel queued in front on ctx->stream (`a` is not
 // read then) / the gate that kernel decided (check_tx_sig's sighash-type rule)
-static int run_small(lamd_ctx *ctx, int mode, size_t n, const u8 *a, const u8 *sig, const u8 *key, int keylen, size_t keystride, u8 *ok,
-                     const u8 *d_a32 = nullptr, const u8 *d_gate = nullptr) {
+int run_small(lamd_ctx *ctx, int mode, size_t n, const u8 *a, const u8 *sig, const u8 *key, int keylen, size_t keystride, u8 *ok, const u8 *d_a32,
+              const u8 *d_gate) {
   int rc;
   if (!ctx->h_small) {
     HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_small, SMALL_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
@@ -3410,7 +2495,7 @@ static int run_small(lamd_ctx *ctx, int mode, size_t n, const u8 *a, const u8 *s
 // does a host-buffer call of `rows` signature rows take the one-launch path?  (LAMD_KEYED=1 -- tests forcing the table-building path -- keeps
 // calls of more than one block on the general path.  A cache-off engine takes it too: such an engine sends a small batch down the ladder
 // either way, and the in-kernel ladder is the faster of the two -- 0.57 against 0.73 ms for a 484-row commitment, GPU session ah.)
-static bool small_path(const lamd_ctx *ctx, size_t rows) {
+bool small_path(const lamd_ctx *ctx, size_t rows) {
   if (!ctx->small_kernel || rows > SMALL_MAX) return false;
   return rows <= 64 || ctx->keyed_mode <= 0;
 }
@@ -3550,366 +2635,15 @@ extern "C" int lamd_pubkey_parse_batch(lamd_ctx *ctx, size_t n, const uint8_t *p
     }
   return LAMD_OK;
 }
-
-// ---- check_tx_sig batches
-extern "C" int lamd_check_tx_sig_batch(lamd_ctx *ctx, size_t n, const uint8_t *preimages, const uint64_t *off, const uint8_t *sighash_type,
-                                       const uint8_t *has_witness, const uint8_t *sig64, const uint8_t *pub, size_t publen, size_t pubstride,
-                                       uint8_t *ok) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!preimages || !off || !sighash_type || !has_witness || !sig64 || !pub || !ok || (publen != 33 && publen != 65) || pubstride < publen) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  size_t keybytes;
-  if (!lamd::key_column_bytes(n, publen, pubstride, &keybytes)) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  // a few rows (an unmodified channeld checks ONE signature per check_tx_sig() call, channeld.c:2171,2224): gate + double SHA-256 on the
-  // host -- the kernel's own inline function -- and the rows through the one-launch latency path
-  if (small_path(ctx, n) && ctx->keyed_mode <= 0) {
-    if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
-    std::vector<u8> hs(32 * n), gate(n);
-    for (size_t i = 0; i < n; i++) gate[i] = txsig_hash_one(preimages + off[i], (size_t)(off[i + 1] - off[i]), sighash_type[i], has_witness[i] != 0, &hs[32 * i]);
-    rc = run_small(ctx, MODE_ECDSA, n, hs.data(), sig64, pub, (int)publen, pubstride, ok);
-    if (rc == LAMD_OK) {
-      for (size_t i = 0; i < n; i++)
-        if (!gate[i]) ok[i] = 0;
-      return LAMD_OK;
-    }
-    if (rc != 1) return rc;
-    ctx->force_learn = true;
-  }
-  const size_t total = off[n] - off[0];
-  std::vector<u64> rel(n + 1);
-  for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-  if ((rc = ensure(ctx, &ctx->g_msgs, total + 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_off, (n + 1) * 8)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_ids, 2 * n)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_c, keybytes)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->out, n)) != LAMD_OK) return rc;
-  u8 *d_types = ctx->g_ids.as<u8>(), *d_wit = d_types + n;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->g_msgs.p, preimages + off[0], total, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->g_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d_types, sighash_type, n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d_wit, has_witness, n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_b.p, sig64, n * 64, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, keybytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_txsig_hash, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(),
-                     (const u8 *)d_types, (const u8 *)d_wit, ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>());
-  HIPCHK(ctx, hipGetLastError());
-  rc = run_device(ctx, MODE_ECDSA, n, ctx->in_a.as<const u8>(), ctx->in_b.as<const u8>(), ctx->in_c.as<const u8>(), (int)publen, pubstride,
-                  ctx->out.as<u8>());
-  ctx->force_learn = false;
-  if (rc != LAMD_OK) return rc;
-  hipLaunchKernelGGL(k_apply_gate, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, ctx->g_malformed.as<const u8>(), ctx->out.as<u8>());
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(ok, ctx->out.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  return lamd_synchronize(ctx);
-}
-
-// ---- check_tx_sig from transaction templates: the templates of a call as ONE staging blob (fixed-width columns first, 16-byte aligned, then the
-// three byte strings; offsets relative to the call's first row) and the hashing kernel over it
-struct txsig_blob {
-  std::vector<u8> st;
-  size_t o_inoff, o_outoff, o_scoff, o_amt, o_ver, o_lock, o_inum, o_nout, o_type, o_wit, o_in, o_out, o_sc, o_hdone, o_hhash, total;
-};
-// A row whose transaction has long lists (a commitment transaction with its 485 outputs: 20 KB under hashOutputs) or a very long script is hashed on the HOST
-// while the blob is packed: SHA-256 is sequential, one lane needed ~6.5 ms for the 20 KB (measured: the whole 484-row call took that long), a host core
-// ~0.1 ms; and the device's per-lane message buffer (k_txsig_tx_hash) holds 951 bytes per stream.  host_done: 0 = the device hashes the row, 1 = hashed here
-// and the gate passed, 2 = hashed here and the gate refused.
-constexpr size_t TXSIG_DEV_MAX_OUT = 900, TXSIG_DEV_MAX_IN = 25, TXSIG_DEV_MAX_SCRIPT = 700;  // each stream of a device row stays below TXH_MAX_STREAM
-static_assert(TXSIG_DEV_MAX_OUT <= TXH_MAX_STREAM && 36 * TXSIG_DEV_MAX_IN <= TXH_MAX_STREAM && TXSIG_DEV_MAX_SCRIPT + 165 <= TXH_MAX_STREAM, "device rows must fit the lane buffer");
-static void txsig_pack(txsig_blob &B, size_t n, const uint32_t *version, const uint32_t *locktime, const uint8_t *inputs40, const uint64_t *in_off,
-                       const uint32_t *input_num, const uint64_t *amount_sat, const uint8_t *outputs, const uint64_t *out_off, const uint32_t *n_outputs,
-                       const uint8_t *scripts, const uint64_t *script_off, const uint8_t *sighash_type, const uint8_t *has_witness) {
-  const size_t nin = (size_t)(in_off[n] - in_off[0]), nout_b = (size_t)(out_off[n] - out_off[0]), nsc = (size_t)(script_off[n] - script_off[0]);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-  B.o_inoff = take((n + 1) * 8); B.o_outoff = take((n + 1) * 8); B.o_scoff = take((n + 1) * 8); B.o_amt = take(n * 8); B.o_ver = take(n * 4);
-  B.o_lock = take(n * 4); B.o_inum = take(n * 4); B.o_nout = take(n * 4); B.o_type = take(n); B.o_wit = take(n); B.o_in = take(nin * 40 + 16);
-  B.o_out = take(nout_b + 16); B.o_sc = take(nsc + 16); B.o_hdone = take(n); B.o_hhash = take(32 * n); B.total = o;
-  B.st.assign(B.total, 0);
-  std::vector<u8> &st = B.st;
-  auto rel = [&](size_t at, const uint64_t *src) { for (size_t i = 0; i <= n; i++) ((u64 *)&st[at])[i] = src[i] - src[0]; };
-  rel(B.o_inoff, in_off); rel(B.o_outoff, out_off); rel(B.o_scoff, script_off);
-  memcpy(&st[B.o_amt], amount_sat, n * 8); memcpy(&st[B.o_ver], version, n * 4); memcpy(&st[B.o_lock], locktime, n * 4);
-  memcpy(&st[B.o_inum], input_num, n * 4); memcpy(&st[B.o_nout], n_outputs, n * 4); memcpy(&st[B.o_type], sighash_type, n); memcpy(&st[B.o_wit], has_witness, n);
-  memcpy(&st[B.o_in], inputs40 + 40 * in_off[0], nin * 40); memcpy(&st[B.o_out], outputs + out_off[0], nout_b); memcpy(&st[B.o_sc], scripts + script_off[0], nsc);
-  for (size_t i = 0; i < n; i++)
-    if ((size_t)(out_off[i + 1] - out_off[i]) > TXSIG_DEV_MAX_OUT || (size_t)(in_off[i + 1] - in_off[i]) > TXSIG_DEV_MAX_IN ||
-        (size_t)(script_off[i + 1] - script_off[i]) > TXSIG_DEV_MAX_SCRIPT) {
-      const bool pass = txsig_tx_hash_one(i, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type,
-                                          has_witness, &st[B.o_hhash + 32 * i]);
-      st[B.o_hdone + i] = pass ? 1 : 2;
-    }
-}
-// BIP143 hash + gate of every row of the blob at `d` (device memory, or pinned device-mapped host memory) -> d_hash32, d_gate
-static int txsig_hash_launch(lamd_ctx *ctx, size_t n, const txsig_blob &B, const u8 *d, u8 *d_hash32, u8 *d_gate) {
-  hipLaunchKernelGGL(k_txsig_tx_hash, dim3((unsigned)((n + TXH_LANES - 1) / TXH_LANES)), dim3(TXH_LANES), 0, ctx->stream, n, (const u32 *)(d + B.o_ver), (const u32 *)(d + B.o_lock), d + B.o_in,
-                     (const u64 *)(d + B.o_inoff), (const u32 *)(d + B.o_inum), (const u64 *)(d + B.o_amt), d + B.o_out, (const u64 *)(d + B.o_outoff),
-                     (const u32 *)(d + B.o_nout), d + B.o_sc, (const u64 *)(d + B.o_scoff), d + B.o_type, d + B.o_wit, d + B.o_hdone, d + B.o_hhash, d_hash32, d_gate);
-  HIPCHK(ctx, hipGetLastError());
+int launch_key_validity(lamd_ctx *ctx, hipStream_t stream, size_t n, const u8 *key33, u32 *qwords, u8 *keyok) {
+  hipLaunchKernelGGL(k_keys, dim3(blocks_for(n)), dim3(256), 0, stream, n, key33, 33, (size_t)33, (const u32 *)nullptr, qwords, keyok, (const u32 *)nullptr);
+  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return LAMD_ERR_HIP; }
   return LAMD_OK;
-}
-// the general path: templates to the device, BIP143 hashes there, the batch machinery, the gate, verdicts back
-static int txsig_tx_general(lamd_ctx *ctx, size_t n, const uint32_t *version, const uint32_t *locktime, const uint8_t *inputs40, const uint64_t *in_off,
-                            const uint32_t *input_num, const uint64_t *amount_sat, const uint8_t *outputs, const uint64_t *out_off, const uint32_t *n_outputs,
-                            const uint8_t *scripts, const uint64_t *script_off, const uint8_t *sighash_type, const uint8_t *has_witness, const uint8_t *sig64,
-                            const uint8_t *pub, size_t publen, size_t pubstride, uint8_t *ok) {
-  int rc;
-  size_t keybytes;
-  if (!lamd::key_column_bytes(n, publen, pubstride, &keybytes)) { ctx->err = "bad argument"; ctx->force_learn = false; return LAMD_ERR_ARG; }
-  txsig_blob B;
-  txsig_pack(B, n, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type, has_witness);
-  if ((rc = ensure(ctx, &ctx->g_msgs, B.total)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_c, keybytes)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->out, n)) != LAMD_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->g_msgs.p, B.st.data(), B.total, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_b.p, sig64, n * 64, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, pub, keybytes, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = txsig_hash_launch(ctx, n, B, ctx->g_msgs.as<const u8>(), ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>())) != LAMD_OK) return rc;
-  rc = run_device(ctx, MODE_ECDSA, n, ctx->in_a.as<const u8>(), ctx->in_b.as<const u8>(), ctx->in_c.as<const u8>(), (int)publen, pubstride,
-                  ctx->out.as<u8>());
-  ctx->force_learn = false;
-  if (rc != LAMD_OK) return rc;
-  hipLaunchKernelGGL(k_apply_gate, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, ctx->g_malformed.as<const u8>(), ctx->out.as<u8>());
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(ok, ctx->out.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  return lamd_synchronize(ctx);  // (B.st is pageable: the runtime staged it before hipMemcpyAsync returned)
-}
-
-// <= SMALL_MAX rows with the BIP143 hashes made ON THE DEVICE: the templates go into a pinned block, ONE asynchronous copy takes them to HBM, k_txsig_tx_hash
-// leaves hashes and gate in device memory, k_small_verify -- queued right behind it -- takes them from there.  One small copy, two launches.  (Hashing on
-// the host, which the small callers do for a handful of rows, is ~12 SHA-256 compressions per row: 1.7 ms for a 484-row commitment, 14 ms for eight of them.)
-// LAMD_OK: verdicts in ok[]; 1: a key the latency path met before without a table is back -- the caller takes the batch path (force_learn is set).
-static int txsig_small_device(lamd_ctx *ctx, size_t n, const uint32_t *version, const uint32_t *locktime, const uint8_t *inputs40, const uint64_t *in_off,
-                              const uint32_t *input_num, const uint64_t *amount_sat, const uint8_t *outputs, const uint64_t *out_off, const uint32_t *n_outputs,
-                              const uint8_t *scripts, const uint64_t *script_off, const uint8_t *sighash_type, const uint8_t *has_witness, const uint8_t *sig64,
-                              const uint8_t *pub, size_t publen, size_t pubstride, uint8_t *ok) {
-  int rc;
-  txsig_blob B;
-  txsig_pack(B, n, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type, has_witness);
-  if (ctx->h_tmpl_cap < B.total) {
-    if (ctx->h_tmpl) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(ctx->h_tmpl); ctx->h_tmpl = nullptr; ctx->h_tmpl_cap = 0; }
-    const size_t want = B.total + B.total / 2 + 4096;
-    HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_tmpl, want, hipHostMallocMapped | hipHostMallocCoherent));
-    ctx->h_tmpl_cap = want;
-  }
-  if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_msgs, B.total)) != LAMD_OK) return rc;
-  memcpy(ctx->h_tmpl, B.st.data(), B.total);
-  // one asynchronous copy of the block (pinned -> HBM, ~250 B per row), then the hashing kernel over HBM.  The first version of this path let the kernel
-  // read the templates where they lay, through the device mapping of the pinned block: 484 lanes walking ~250 bytes each byte by byte over PCIe took 6.5 ms
-  // (rocprofv3, tools/commit_trace_probe.py) -- reading host memory from a kernel is fine for one 161-byte row, not for a SHA-256 input stream.
-  HIPCHK(ctx, hipMemcpyAsync(ctx->g_msgs.p, ctx->h_tmpl, B.total, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = txsig_hash_launch(ctx, n, B, ctx->g_msgs.as<const u8>(), ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>())) != LAMD_OK) return rc;
-  rc = run_small(ctx, MODE_ECDSA, n, nullptr, sig64, pub, (int)publen, pubstride, ok, ctx->in_a.as<const u8>(), ctx->g_malformed.as<const u8>());
-  if (rc == 1) ctx->force_learn = true;
-  return rc;
-}
-
-extern "C" int lamd_check_tx_sig_tx_batch(lamd_ctx *ctx, size_t n, const uint32_t *version, const uint32_t *locktime, const uint8_t *inputs40,
-                                          const uint64_t *in_off, const uint32_t *input_num, const uint64_t *amount_sat, const uint8_t *outputs,
-                                          const uint64_t *out_off, const uint32_t *n_outputs, const uint8_t *scripts, const uint64_t *script_off,
-                                          const uint8_t *sighash_type, const uint8_t *has_witness, const uint8_t *sig64, const uint8_t *pub,
-                                          size_t publen, size_t pubstride, uint8_t *ok) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!version || !locktime || !inputs40 || !in_off || !input_num || !amount_sat || !outputs || !out_off || !n_outputs || !scripts || !script_off ||
-      !sighash_type || !has_witness || !sig64 || !pub || !ok || (publen != 33 && publen != 65) || pubstride < publen) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
-  if (small_path(ctx, n) && ctx->keyed_mode <= 0 && n <= TXSIG_HOST_HASH_ROWS) {
-    // a handful of rows: BIP143 hash on the host (the kernels' own inline function), rows through the latency path in ONE launch
-    std::vector<u8> hs(32 * n), gate(n);
-    for (size_t i = 0; i < n; i++)
-      gate[i] = txsig_tx_hash_one(i, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type,
-                                  has_witness, &hs[32 * i]);
-    rc = run_small(ctx, MODE_ECDSA, n, hs.data(), sig64, pub, (int)publen, pubstride, ok);
-    if (rc == LAMD_OK) {
-      for (size_t i = 0; i < n; i++)
-        if (!gate[i]) ok[i] = 0;
-      return LAMD_OK;
-    }
-    if (rc != 1) return rc;
-    ctx->force_learn = true;
-  } else if (small_path(ctx, n) && ctx->keyed_mode <= 0) {  // up to 4 096 rows (several commitments at once: lamd_served's merged call): hashes on the device
-    rc = txsig_small_device(ctx, n, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type, has_witness,
-                            sig64, pub, publen, pubstride, ok);
-    if (rc != 1) return rc;
-  }
-  return txsig_tx_general(ctx, n, version, locktime, inputs40, in_off, input_num, amount_sat, outputs, out_off, n_outputs, scripts, script_off, sighash_type,
-                          has_witness, sig64, pub, publen, pubstride, ok);
-}
-
-// ---- one commitment_signed as ONE call (channeld/channeld.c:2171-2232): include/lightning_amd.h
-extern "C" int lamd_check_commitment_signed(lamd_ctx *ctx, const lamd_tx_template *commit_tx, const uint8_t remote_funding33[33], const uint8_t commit_sig64[64],
-                                            uint8_t commit_sighash_type, size_t n_htlc, const lamd_tx_template *htlc_txs, const uint8_t remote_htlckey33[33],
-                                            const uint8_t *htlc_sigs64, const uint8_t *htlc_sighash_types, int64_t *first_bad, uint8_t *ok_rows) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!commit_tx || !remote_funding33 || !commit_sig64 || !first_bad || (n_htlc && (!htlc_txs || !remote_htlckey33 || !htlc_sigs64 || !htlc_sighash_types))) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  *first_bad = 0;  // fails closed: an error return never leaves "all good" behind
-  const size_t n = 1 + n_htlc;
-  // the 1 + N (transaction, input 0 .. , signature) rows in the reference's order: row 0 the commitment transaction under the funding key,
-  // row 1 + i HTLC transaction i under the htlc key
-  std::vector<uint32_t> version(n), locktime(n), input_num(n), n_outputs(n);
-  std::vector<uint64_t> in_off(n + 1), out_off(n + 1), sc_off(n + 1), amount(n);
-  std::vector<u8> type(n), wit(n, 1), sig(64 * n), pub(33 * n);
-  size_t nin = 0, nout = 0, nsc = 0;
-  for (size_t i = 0; i < n; i++) {
-    const lamd_tx_template *t = i ? &htlc_txs[i - 1] : commit_tx;
-    if ((t->n_inputs && !t->inputs40) || (t->outputs_len && !t->outputs) || (t->script_len && !t->script)) {
-      ctx->err = "bad argument: transaction template with a null array";
-      return LAMD_ERR_ARG;
-    }
-    in_off[i] = nin; out_off[i] = nout; sc_off[i] = nsc;
-    nin += t->n_inputs; nout += t->outputs_len; nsc += t->script_len;
-  }
-  in_off[n] = nin; out_off[n] = nout; sc_off[n] = nsc;
-  std::vector<u8> inputs(40 * nin + 1), outputs(nout + 1), scripts(nsc + 1);
-  for (size_t i = 0; i < n; i++) {
-    const lamd_tx_template *t = i ? &htlc_txs[i - 1] : commit_tx;
-    version[i] = t->version; locktime[i] = t->locktime; input_num[i] = t->input_num; n_outputs[i] = t->n_outputs; amount[i] = t->amount_sat;
-    if (t->n_inputs) memcpy(&inputs[40 * in_off[i]], t->inputs40, 40 * (size_t)t->n_inputs);
-    if (t->outputs_len) memcpy(&outputs[out_off[i]], t->outputs, t->outputs_len);
-    if (t->script_len) memcpy(&scripts[sc_off[i]], t->script, t->script_len);
-    type[i] = i ? htlc_sighash_types[i - 1] : commit_sighash_type;
-    memcpy(&sig[64 * i], i ? htlc_sigs64 + 64 * (i - 1) : commit_sig64, 64);
-    memcpy(&pub[33 * i], i ? remote_htlckey33 : remote_funding33, 33);
-  }
-  std::vector<u8> okv(n, 0);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
-  bool done = false;
-  if (small_path(ctx, n) && ctx->keyed_mode <= 0) {
-    rc = txsig_small_device(ctx, n, version.data(), locktime.data(), inputs.data(), in_off.data(), input_num.data(), amount.data(), outputs.data(), out_off.data(),
-                            n_outputs.data(), scripts.data(), sc_off.data(), type.data(), wit.data(), sig.data(), pub.data(), 33, 33, okv.data());
-    if (rc == LAMD_OK) done = true;
-    else if (rc != 1) return rc;   // 1: a key the latency path met before without a table is back (the channel's htlc key): built and published below
-  }
-  if (!done) {
-    rc = txsig_tx_general(ctx, n, version.data(), locktime.data(), inputs.data(), in_off.data(), input_num.data(), amount.data(), outputs.data(), out_off.data(),
-                          n_outputs.data(), scripts.data(), sc_off.data(), type.data(), wit.data(), sig.data(), pub.data(), 33, 33, okv.data());
-    if (rc != LAMD_OK) return rc;
-  }
-  int64_t bad = -1;
-  for (size_t i = 0; i < n && bad < 0; i++)
-    if (!okv[i]) bad = (int64_t)i;  // 0: the commitment signature (:2171), 1 + i: htlc_sigs[i] (:2224) -- the first in the reference's order
-  *first_bad = bad;
-  if (ok_rows) memcpy(ok_rows, okv.data(), n);
-  return LAMD_OK;
-}
-
-// ---- BOLT #12 signatures: n independent bolt12_check_signature(fields, messagename, fieldname, key, sig) calls (common/bolt12.c:80-92)
-static int bolt12_hash_device(lamd_ctx *ctx, size_t n, const uint8_t *tlvs, const uint64_t *off, const char *messagename, const char *fieldname,
-                              u8 *d_root, u8 *d_msg, u8 *d_valid) {
-  const size_t total = (size_t)(off[n] - off[0]);
-  std::vector<u64> rel(n + 1);
-  for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-  int rc;
-  if ((rc = ensure(ctx, &ctx->g_msgs, total + 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_off, (n + 1) * 8)) != LAMD_OK) return rc;
-  bolt12_mids mids;
-  const u8 leaf[6] = {'L', 'n', 'L', 'e', 'a', 'f'}, branch[8] = {'L', 'n', 'B', 'r', 'a', 'n', 'c', 'h'};
-  bolt12_tag_midstate(leaf, 6, leaf, 0, mids.leaf);
-  bolt12_tag_midstate(branch, 8, branch, 0, mids.branch);
-  const std::string tag2 = std::string(messagename) + fieldname;   // "lightning" || messagename || fieldname (bitcoin/signature.c:389-405)
-  bolt12_tag_midstate((const u8 *)"lightning", 9, (const u8 *)tag2.data(), tag2.size(), mids.sig);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->g_msgs.p, tlvs + off[0], total, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->g_off.p, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // rel lives on this frame
-  hipLaunchKernelGGL(k_bolt12_hash, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(), mids,
-                     d_root, d_msg, d_valid);
-  HIPCHK(ctx, hipGetLastError());
-  return LAMD_OK;
-}
-extern "C" int lamd_bolt12_merkle_batch(lamd_ctx *ctx, size_t n, const uint8_t *tlvs, const uint64_t *off, const char *messagename,
-                                        const char *fieldname, uint8_t *merkle32, uint8_t *sighash32, uint8_t *ok) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!tlvs || !off || !messagename || !fieldname || !ok) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
-  if ((rc = bolt12_hash_device(ctx, n, tlvs, off, messagename, fieldname, ctx->in_b.as<u8>(), ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>())) != LAMD_OK) return rc;
-  if (merkle32) HIPCHK(ctx, hipMemcpyAsync(merkle32, ctx->in_b.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  if (sighash32) HIPCHK(ctx, hipMemcpyAsync(sighash32, ctx->in_a.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ok, ctx->g_malformed.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  return lamd_synchronize(ctx);
-}
-extern "C" int lamd_bolt12_check_signature_batch(lamd_ctx *ctx, size_t n, const uint8_t *tlvs, const uint64_t *off, const char *messagename,
-                                                 const char *fieldname, const uint8_t *key33, size_t keystride, const uint8_t *sig64, uint8_t *ok) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!tlvs || !off || !messagename || !fieldname || !key33 || keystride < 33 || !sig64 || !ok) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
-  // check_schnorr_sig serialises the key compressed and drops the parity byte (bitcoin/signature.c:417-422)
-  std::vector<u8> xonly(n * 32);
-  for (size_t i = 0; i < n; i++) memcpy(&xonly[32 * i], key33 + keystride * i + 1, 32);
-  // a few invoices / offers (one per bolt12_check_signature() call, common/bolt12.c:80-92): merkle root and tagged hash on the host --
-  // the kernel's own inline functions (bolt12.h) -- and the rows through the one-launch latency path
-  if (n <= 256 && small_path(ctx, n) && ctx->keyed_mode <= 0) {
-    bolt12_mids mids;
-    const u8 leaf[6] = {'L', 'n', 'L', 'e', 'a', 'f'}, branch[8] = {'L', 'n', 'B', 'r', 'a', 'n', 'c', 'h'};
-    bolt12_tag_midstate(leaf, 6, leaf, 0, mids.leaf);
-    bolt12_tag_midstate(branch, 8, branch, 0, mids.branch);
-    const std::string tag2 = std::string(messagename) + fieldname;
-    bolt12_tag_midstate((const u8 *)"lightning", 9, (const u8 *)tag2.data(), tag2.size(), mids.sig);
-    std::vector<u8> msg(32 * n, 0), valid(n);
-    for (size_t i = 0; i < n; i++) {
-      u8 root[32];
-      valid[i] = bolt12_merkle_root(tlvs + off[i], (size_t)(off[i + 1] - off[i]), mids, root);
-      if (valid[i]) bolt12_sighash(mids, root, &msg[32 * i]);
-    }
-    rc = run_small(ctx, MODE_SCHNORR, n, msg.data(), sig64, xonly.data(), 32, 32, ok);
-    if (rc == LAMD_OK) {
-      for (size_t i = 0; i < n; i++)
-        if (!valid[i]) ok[i] = 0;
-      return LAMD_OK;
-    }
-    if (rc != 1) return rc;
-    ctx->force_learn = true;
-  }
-  if ((rc = ensure(ctx, &ctx->in_a, n * 32)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_b, n * 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->in_c, n * 32)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_malformed, n)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->out, n)) != LAMD_OK) return rc;
-  if ((rc = bolt12_hash_device(ctx, n, tlvs, off, messagename, fieldname, nullptr, ctx->in_a.as<u8>(), ctx->g_malformed.as<u8>())) != LAMD_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_b.p, sig64, n * 64, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->in_c.p, xonly.data(), n * 32, hipMemcpyHostToDevice, ctx->stream));
-  rc = run_device(ctx, MODE_SCHNORR, n, ctx->in_a.as<const u8>(), ctx->in_b.as<const u8>(), ctx->in_c.as<const u8>(), 32, 32, ctx->out.as<u8>());
-  ctx->force_learn = false;
-  if (rc != LAMD_OK) return rc;
-  hipLaunchKernelGGL(k_apply_gate, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, ctx->g_malformed.as<const u8>(), ctx->out.as<u8>());
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(ok, ctx->out.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  return lamd_synchronize(ctx);   // xonly lives on this frame
 }
 
 // ---- ECDSA public-key recovery (verify_core.h "ECDSA public-key recovery"): out_pub33[i] = the compressed key, ok[i] = 1, or
 // a zeroed key and ok[i] = 0 where libsecp256k1's parse/recover would fail
-static int recover_device(lamd_ctx *ctx, size_t n, const u8 *d_hash, const u8 *d_sig, const u8 *d_recid, u8 *d_pub33, u8 *d_ok) {
+int recover_device(lamd_ctx *ctx, size_t n, const u8 *d_hash, const u8 *d_sig, const u8 *d_recid, u8 *d_pub33, u8 *d_ok) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc;
   for (size_t o = 0; o < n; o += ctx->chunk) {
@@ -3968,268 +2702,11 @@ extern "C" int lamd_ecdsa_recover_batch(lamd_ctx *ctx, size_t n, const uint8_t *
   return lamd_synchronize(ctx);
 }
 
-// ---- signatures from their text: BOLT #11 invoices and signed messages (bolt11.h).  The front-end kernel, the key-parse kernel, the verification
-// batch, the recovery batch and the merge are queued on the context's stream without the host waiting in between; both batches run over all
-// n rows (k_bolt11_front on how the rows that do not belong to a batch leave it at once).
-struct text_cols {
-  int8_t *pre, *status;
-  u8 *hash, *sig, *sig_ver, *key, *recid_rec, *have_n, *keyok, *ok_ver, *ok_rec, *pub_rec, *node_id;
-  u32 *qwords;
-};
-static size_t text_cols_bytes(size_t n) { return n * (64 + 32 + 64 + 64 + 33 + 33 + 33 + 7) + 64; }
-static text_cols text_cols_at(u8 *p, size_t n) {
-  text_cols c;
-  c.qwords = (u32 *)p; p += 64 * n;     // what k_keys writes next to keyok (16-byte aligned: uint4 stores); never read
-  c.hash = p; p += 32 * n;              // 4-byte aligned
-  c.sig = p; p += 64 * n;
-  c.sig_ver = p; p += 64 * n;
-  c.key = p; p += 33 * n;
-  c.pub_rec = p; p += 33 * n;
-  c.node_id = p; p += 33 * n;
-  c.pre = (int8_t *)p; p += n;
-  c.status = (int8_t *)p; p += n;
-  c.recid_rec = p; p += n;
-  c.have_n = p; p += n;
-  c.keyok = p; p += n;
-  c.ok_ver = p; p += n;
-  c.ok_rec = p;
-  return c;
-}
-// strings back to back on the device, offsets relative to the first; `rel` must outlive the copies
-static int text_upload(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, devbuf *d_strs, size_t at, u64 *d_off, std::vector<u64> &rel) {
-  const size_t total = (size_t)(off[n] - off[0]);
-  rel.resize(n + 1);
-  for (size_t i = 0; i <= n; i++) {
-    if (off[i] < off[0] || (i && off[i] < off[i - 1])) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
-    rel[i] = off[i] - off[0] + at;
-  }
-  if (total) HIPCHK(ctx, hipMemcpyAsync(d_strs->as<u8>() + at, strs + off[0], total, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(d_off, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  return LAMD_OK;
-}
-static int text_timing_begin(lamd_ctx *ctx) {
-  if (!ctx->timing) return LAMD_OK;
-  for (auto &e : ctx->ev_text)
-    if (!e) HIPCHK(ctx, hipEventCreate(&e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev_text[0], ctx->stream));
-  return LAMD_OK;
-}
-static int text_timing_end(lamd_ctx *ctx) {   // behind the synchronisation that ends the call
-  if (!ctx->timing) return LAMD_OK;
-  for (int k = 0; k < 2; k++) {
-    float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev_text[k], ctx->ev_text[k + 1]));
-    ctx->text_ms[k] = ms;
-  }
-  return LAMD_OK;
-}
-extern "C" int lamd_bolt11_check_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, int8_t *status, uint8_t *node_id33,
-                                       uint8_t *hash32, uint8_t *have_n) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!strs || !off || !status || !node_id33) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
-  if (off[n] < off[0]) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
-  if ((rc = ensure(ctx, &ctx->g_msgs, (size_t)(off[n] - off[0]) + 64)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->g_off, (n + 1) * 8)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->tx_cols, text_cols_bytes(n))) != LAMD_OK) return rc;
-  const text_cols c = text_cols_at(ctx->tx_cols.as<u8>(), n);
-  std::vector<u64> rel;   // the queued copy reads it: lives until the stream has been synchronised
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return code;
-  };
-  if ((rc = text_upload(ctx, n, strs, off, &ctx->g_msgs, 0, ctx->g_off.as<u64>(), rel)) != LAMD_OK) return fail(rc);
-  if ((rc = text_timing_begin(ctx)) != LAMD_OK) return fail(rc);
-  hipLaunchKernelGGL(k_bolt11_front, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(), c.pre,
-                     c.hash, c.sig, c.recid_rec, c.sig_ver, c.key, c.have_n);
-  if (ctx->timing && hipEventRecord(ctx->ev_text[1], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
-  // the key-parse kernel for its validity byte alone (its affine words in c.qwords are not read again): the verification batch parses the keys it
-  // needs once more, but reports validity only for the rows its early reject lets through, and a bad `n` key counts whatever the signature bytes are
-  hipLaunchKernelGGL(k_keys, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const u8 *)c.key, 33, (size_t)33, (const u32 *)nullptr, c.qwords, c.keyok,
-                     (const u32 *)nullptr);
-  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return fail(LAMD_ERR_HIP); }
-  if ((rc = run_device(ctx, MODE_ECDSA, n, c.hash, c.sig_ver, c.key, 33, 33, c.ok_ver)) != LAMD_OK) return fail(rc);
-  if ((rc = recover_device(ctx, n, c.hash, c.sig, c.recid_rec, c.pub_rec, c.ok_rec)) != LAMD_OK) return fail(rc);
-  hipLaunchKernelGGL(k_text_merge, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const int8_t *)c.pre, c.have_n, (const u8 *)c.keyok, (const u8 *)c.ok_ver,
-                     (const u8 *)c.ok_rec, (const u8 *)c.pub_rec, (const u8 *)c.key, c.hash, (int)LAMD_B11_NO_KEY, c.status, c.node_id);
-  if (hipGetLastError() != hipSuccess) { ctx->err = "text merge: launch failed"; return fail(LAMD_ERR_HIP); }
-  if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
-  hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(node_id33, c.node_id, n * 33, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && hash32) e = hipMemcpyAsync(hash32, c.hash, n * 32, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && have_n) e = hipMemcpyAsync(have_n, c.have_n, n, hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
-  if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
-  return text_timing_end(ctx);
-}
-extern "C" int lamd_checkmessage_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *moff, const uint8_t *zbase, const uint64_t *zoff,
-                                       int8_t *status, uint8_t *node_id33) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!msgs || !moff || !zbase || !zoff || !status || !node_id33) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if (moff[n] < moff[0] || zoff[n] < zoff[0]) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
-  const size_t mbytes = (size_t)(moff[n] - moff[0]), zbytes = (size_t)(zoff[n] - zoff[0]);
-  if ((rc = ensure(ctx, &ctx->g_msgs, mbytes + zbytes + 64)) != LAMD_OK) return rc;   // messages | signature strings
-  if ((rc = ensure(ctx, &ctx->g_off, 2 * (n + 1) * 8)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->tx_cols, text_cols_bytes(n))) != LAMD_OK) return rc;
-  const text_cols c = text_cols_at(ctx->tx_cols.as<u8>(), n);
-  std::vector<u64> mrel, zrel;
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return code;
-  };
-  u64 *d_moff = ctx->g_off.as<u64>(), *d_zoff = d_moff + n + 1;
-  if ((rc = text_upload(ctx, n, msgs, moff, &ctx->g_msgs, 0, d_moff, mrel)) != LAMD_OK) return fail(rc);
-  if ((rc = text_upload(ctx, n, zbase, zoff, &ctx->g_msgs, mbytes, d_zoff, zrel)) != LAMD_OK) return fail(rc);
-  if ((rc = text_timing_begin(ctx)) != LAMD_OK) return fail(rc);
-  hipLaunchKernelGGL(k_checkmessage_front, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), (const u64 *)d_moff,
-                     ctx->g_msgs.as<const u8>(), (const u64 *)d_zoff, c.pre, c.hash, c.sig, c.recid_rec);
-  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return fail(LAMD_ERR_HIP); }
-  if (ctx->timing && hipEventRecord(ctx->ev_text[1], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
-  if ((rc = recover_device(ctx, n, c.hash, c.sig, c.recid_rec, c.pub_rec, c.ok_rec)) != LAMD_OK) return fail(rc);
-  hipLaunchKernelGGL(k_text_merge, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const int8_t *)c.pre, (u8 *)nullptr, (const u8 *)nullptr, (const u8 *)nullptr,
-                     (const u8 *)c.ok_rec, (const u8 *)c.pub_rec, (const u8 *)nullptr, c.hash, (int)LAMD_MSG_NO_KEY, c.status, c.node_id);
-  if (hipGetLastError() != hipSuccess) { ctx->err = "text merge: launch failed"; return fail(LAMD_ERR_HIP); }
-  if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
-  hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(node_id33, c.node_id, n * 33, hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
-  if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
-  return text_timing_end(ctx);
-}
-
-// ---- BOLT #12 offers, invoice requests and invoices from their text (bolt12_text.h): lamd_bolt11_check_batch step for step, with the BIP-340 batch in
-// place of the ECDSA and recovery batches.  The decode scratch lies behind the strings in the same buffer.
-struct b12_cols {
-  int8_t *pre, *status;
-  u8 *hash, *offer_id, *invreq_id, *sig, *xonly, *key, *signer, *kind, *have_key, *keyok, *ok_ver;
-  u32 *qwords;
-};
-static size_t b12_cols_bytes(size_t n) { return n * (64 + 4 * 32 + 64 + 33 + 33 + 6) + 64; }
-static b12_cols b12_cols_at(u8 *p, size_t n) {
-  b12_cols c;
-  c.qwords = (u32 *)p; p += 64 * n;     // what k_keys writes next to keyok (16-byte aligned: uint4 stores); never read
-  c.hash = p; p += 32 * n;
-  c.xonly = p; p += 32 * n;
-  c.sig = p; p += 64 * n;
-  c.offer_id = p; p += 32 * n;
-  c.invreq_id = p; p += 32 * n;
-  c.key = p; p += 33 * n;
-  c.signer = p; p += 33 * n;
-  c.pre = (int8_t *)p; p += n;
-  c.status = (int8_t *)p; p += n;
-  c.kind = p; p += n;
-  c.have_key = p; p += n;
-  c.keyok = p; p += n;
-  c.ok_ver = p;
-  return c;
-}
-extern "C" int lamd_bolt12_check_text_batch(lamd_ctx *ctx, size_t n, const uint8_t *strs, const uint64_t *off, int8_t *status, uint8_t *kind,
-                                            uint8_t *signer33, uint8_t *sighash32, uint8_t *offer_id32, uint8_t *invreq_id32) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (n == 0) return LAMD_OK;
-  if (!strs || !off || !status || !kind || !signer33) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = cache_maybe_reset(ctx)) != LAMD_OK) return rc;
-  if (off[n] < off[0]) { ctx->err = "offsets must not decrease"; return LAMD_ERR_ARG; }
-  const size_t total = (size_t)(off[n] - off[0]);
-  if ((rc = ensure(ctx, &ctx->g_msgs, 2 * total + 64)) != LAMD_OK) return rc;   // strings | decode scratch
-  if ((rc = ensure(ctx, &ctx->g_off, (n + 1) * 8)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->tx_cols, b12_cols_bytes(n))) != LAMD_OK) return rc;
-  const b12_cols c = b12_cols_at(ctx->tx_cols.as<u8>(), n);
-  bolt12_text_mids mids;
-  bolt12_text_make_mids(&mids);
-  std::vector<u64> rel;   // the queued copy reads it: lives until the stream has been synchronised
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return code;
-  };
-  if ((rc = text_upload(ctx, n, strs, off, &ctx->g_msgs, 0, ctx->g_off.as<u64>(), rel)) != LAMD_OK) return fail(rc);
-  if ((rc = text_timing_begin(ctx)) != LAMD_OK) return fail(rc);
-  hipLaunchKernelGGL(k_bolt12_text_front, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, n, ctx->g_msgs.as<const u8>(), ctx->g_off.as<const u64>(),
-                     ctx->g_msgs.as<u8>() + total, mids, c.pre, c.kind, c.have_key, c.key, c.xonly, c.sig, c.hash, c.offer_id, c.invreq_id);
-  if (ctx->timing && hipEventRecord(ctx->ev_text[1], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
-  // the key-parse kernel for its validity byte alone, as in lamd_bolt11_check_batch: a bad key counts whatever the signature bytes are
-  hipLaunchKernelGGL(k_keys, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const u8 *)c.key, 33, (size_t)33, (const u32 *)nullptr, c.qwords, c.keyok,
-                     (const u32 *)nullptr);
-  if (hipGetLastError() != hipSuccess) { ctx->err = "text front end: launch failed"; return fail(LAMD_ERR_HIP); }
-  if ((rc = run_device(ctx, MODE_SCHNORR, n, c.hash, c.sig, c.xonly, 32, 32, c.ok_ver)) != LAMD_OK) return fail(rc);
-  hipLaunchKernelGGL(k_bolt12_text_merge, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, n, (const int8_t *)c.pre, (const u8 *)c.kind, (const u8 *)c.have_key,
-                     (const u8 *)c.keyok, (const u8 *)c.ok_ver, (const u8 *)c.key, c.hash, c.offer_id, c.invreq_id, c.status, c.signer);
-  if (hipGetLastError() != hipSuccess) { ctx->err = "text merge: launch failed"; return fail(LAMD_ERR_HIP); }
-  if (ctx->timing && hipEventRecord(ctx->ev_text[2], ctx->stream) != hipSuccess) { ctx->err = "hipEventRecord"; return fail(LAMD_ERR_HIP); }
-  hipError_t e = hipMemcpyAsync(status, c.status, n, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(kind, c.kind, n, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(signer33, c.signer, n * 33, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && sighash32) e = hipMemcpyAsync(sighash32, c.hash, n * 32, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && offer_id32) e = hipMemcpyAsync(offer_id32, c.offer_id, n * 32, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && invreq_id32) e = hipMemcpyAsync(invreq_id32, c.invreq_id, n * 32, hipMemcpyDeviceToHost, ctx->stream);
-  if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return fail(LAMD_ERR_HIP); }
-  if ((rc = lamd_synchronize(ctx)) != LAMD_OK) return rc;
-  return text_timing_end(ctx);
-}
-
-// ---- fee grind: see k_grind.  Returns 1 (found; *feerate, *fee set), 0 (no candidate verifies) or an error < 0.
-extern "C" int lamd_grind_htlc_tx_fee(lamd_ctx *ctx, const uint8_t *preimage, size_t preimage_len, const uint8_t *outputs,
-                                      size_t outputs_len, uint64_t input_sat, uint64_t weight, uint32_t min_feerate,
-                                      uint32_t max_feerate, const uint8_t sig64[64], uint8_t sighash_type, int has_witness_script,
-                                      const uint8_t pubkey33[33], uint32_t *feerate, uint64_t *fee) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!preimage || !outputs || !sig64 || !pubkey33 || !feerate || !fee || preimage_len < 40 + 4 || outputs_len < 9 ||
-      outputs_len > (size_t)GRIND_MAX_OUTPUTS || weight == 0 || weight > ((uint64_t)1 << 31)) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  // the sighash-type gate of check_tx_sig (bitcoin/signature.c:206-211) is the same for every candidate
-  if (!(sighash_type == 1 || (sighash_type == 0x83 && has_witness_script))) return 0;
-  if (max_feerate < min_feerate) return 0;
-  const size_t ncand = (size_t)max_feerate - min_feerate + 1;
-  if (ncand > ((size_t)1 << 30)) {
-    ctx->err = "feerate range too large";
-    return LAMD_ERR_ARG;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t lead = ((preimage_len - 40) / 64) * 64, tail_len = preimage_len - lead;  // hashOutputs starts in the first tail block
-  // staging: preimage | outputs | sig | key | setup | best
-  const size_t o_out = (preimage_len + 15) & ~(size_t)15, o_sig = (o_out + outputs_len + 15) & ~(size_t)15, o_key = o_sig + 64,
-               o_setup = o_key + 48, o_best = o_setup + ((sizeof(grind_setup) + 15) & ~(size_t)15), total = o_best + 16;
-  int rc;
-  if ((rc = ensure(ctx, &ctx->g_msgs, total)) != LAMD_OK) return rc;
-  if ((rc = ensure(ctx, &ctx->slots, (size_t)SLOT_WORDS * 4)) != LAMD_OK) return rc;
-  std::vector<u8> stage(total, 0);
-  memcpy(&stage[0], preimage, preimage_len);
-  memcpy(&stage[o_out], outputs, outputs_len);
-  memcpy(&stage[o_sig], sig64, 64);
-  memcpy(&stage[o_key], pubkey33, 33);
-  memset(&stage[o_best], 0xFF, 4);
-  u8 *d = ctx->g_msgs.as<u8>();
-  HIPCHK(ctx, hipMemcpyAsync(d, stage.data(), total, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_grind_setup, dim3(1), dim3(64), 0, ctx->stream, d + o_sig, d + o_key, d, (u32)(lead / 64), ctx->slots.as<u32>(),
-                     (const u32 *)ctx->gtable, (grind_setup *)(d + o_setup));
-  hipLaunchKernelGGL(k_grind, dim3(blocks_for(ncand)), dim3(256), 0, ctx->stream, (u32)ncand, min_feerate, weight, input_sat, d + lead,
-                     (u32)tail_len, (u32)lead, d + o_out, (u32)outputs_len, (const grind_setup *)(d + o_setup), (const u32 *)ctx->gtable,
-                     (u32 *)(d + o_best));
-  HIPCHK(ctx, hipGetLastError());
-  u32 best = 0xFFFFFFFFu;
-  HIPCHK(ctx, hipMemcpyAsync(&best, d + o_best, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (best == 0xFFFFFFFFu) return 0;
-  *feerate = min_feerate + best;
-  *fee = (uint64_t)*feerate * weight / 1000;
-  return 1;
-}
-
 // ---- gossip
 // device core: everything resident.  The signature rows of all messages form one ECDSA batch with 33-byte keys (cut into
 // chunks like any other batch: a message's rows may straddle a chunk); the reduce runs once over all messages.
-static int gossip_device(lamd_ctx *ctx, size_t n, const u8 *d_msgs, const u64 *d_off, const u8 *d_ids, const u64 *d_rowbase, size_t rows,
-                         int8_t *d_verdict, const u64 *d_len = nullptr) {
+int gossip_device(lamd_ctx *ctx, size_t n, const u8 *d_msgs, const u64 *d_off, const u8 *d_ids, const u64 *d_rowbase, size_t rows, int8_t *d_verdict,
+                  const u64 *d_len) {
   int rc;
   if ((rc = ensure(ctx, &ctx->g_hash, rows * 32)) != LAMD_OK) return rc;
   if ((rc = ensure(ctx, &ctx->g_sig, rows * 64)) != LAMD_OK) return rc;
@@ -4287,613 +2764,6 @@ extern "C" int lamd_sigcheck_gossip_spans_device(lamd_ctx *ctx, size_t n, const 
   if (rc != LAMD_OK && L != ctx) ctx->err = L->err;
   return rc;
 }
-
-// ---- gossip_store audit
-static void store_count_verdicts(const int8_t *v, size_t n, lamd_store_summary *s) {
-  for (size_t i = 0; i < n; i++) {
-    switch (v[i]) {
-      case LAMD_STORE_OK: s->ok++; break;
-      case LAMD_STORE_SKIPPED_DELETED: s->skipped_deleted++; break;
-      case LAMD_STORE_BAD_CHECKSUM: s->bad_checksum++; break;
-      case LAMD_STORE_UNKNOWN_TYPE: s->unknown_type++; break;
-      case LAMD_STORE_MALFORMED: s->malformed++; break;
-      case LAMD_STORE_REDUNDANT: s->redundant++; break;
-      case LAMD_STORE_NO_CHANNEL: s->no_channel++; break;
-      default:
-        if (v[i] >= 1 && v[i] <= 4) s->bad_signature[v[i] - 1]++;
-    }
-  }
-  s->clean = s->end_reason == LAMD_STORE_END_EOF && s->ok + s->skipped_deleted == n;
-}
-extern "C" int lamd_gossip_store_frame(const uint8_t *store, size_t len, size_t cap, uint64_t *rec_off, size_t *n_records,
-                                       lamd_store_summary *summary) {
-  if (!store || !n_records || !summary || (cap && !rec_off)) return LAMD_ERR_ARG;
-  *n_records = 0;
-  if (!store_walk(store, len, summary, [&](size_t i, u64 off, const store_hdr &, u32) {
-        if (i < cap) rec_off[i] = off;
-      }))
-    return LAMD_ERR_ARG;
-  *n_records = (size_t)summary->records;
-  return summary->records > cap ? LAMD_ERR_ARG : LAMD_OK;
-}
-// Everything between the host walk and the final copy is queued on one lane's stream: image (unless resident) and the walk's arrays up,
-// four kernels and the signature batch, the verdict bytes down.  store_job: what the queued stages leave on the device for the caller --
-// lamd_gossip_store_audit copies the verdicts down, lamd_gossip_store_repair queues its own stages behind them first.
-struct store_job {
-  lamd_ctx *L = nullptr;      // the lane; nullptr: nothing is queued (no record, or an error before the first copy)
-  size_t n = 0, n_cann = 0;   // records; live channel_announcements
-  const u8 *img = nullptr;    // the image on the device
-  const u64 *d_recoff = nullptr;
-  const u64 *d_keys = nullptr;
-  const u32 *d_vals = nullptr;
-  u32 bits = 0;               // the scid index
-  const int8_t *d_verdict = nullptr;
-  std::vector<u64> pack;      // the queued copy reads it: lives until the stream has been synchronised
-};
-#define STCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { L->err = std::string(#call) + ": " + hipGetErrorString(e_); return fail(LAMD_ERR_HIP); } } while (0)
-static int store_audit_queue(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off, size_t *n_records,
-                             lamd_store_summary *summary, store_job *job) {
-  *n_records = 0;
-  // the walk: record offsets, and the selection of the signature batch -- the live 256 / 257 / 258 records (4 rows / 1 / 1)
-  std::vector<u64> start, mlen, rowbase;
-  std::vector<u32> sel;
-  size_t n_cann = 0;
-  u64 rows = 0;
-  if (!store_walk(store, len, summary, [&](size_t i, u64 off, const store_hdr &h, u32 type) {
-        if (i < cap) rec_off[i] = off;
-        const bool sig = type == STORE_T_CANN || type == STORE_T_NANN || type == STORE_T_CUPD;
-        sel.push_back(sig ? (u32)start.size() : STORE_NONE);
-        if (!sig) return;
-        start.push_back(off + STORE_HDR);
-        mlen.push_back(h.len);
-        rowbase.push_back(rows);
-        rows += type == STORE_T_CANN ? 4 : 1;
-        n_cann += type == STORE_T_CANN;
-      })) {
-    ctx->err = "not a gossip_store of major version 0";
-    return LAMD_ERR_ARG;
-  }
-  const size_t n = (size_t)summary->records, nsel = start.size();
-  *n_records = n;
-  if (n > cap) { ctx->err = "gossip_store audit: rec_off / verdict too small"; return LAMD_ERR_ARG; }
-  if (n >= (size_t)STORE_NONE || rows >= (u64)STORE_NONE) { ctx->err = "gossip_store audit: too many records"; return LAMD_ERR_ARG; }
-  summary->signatures = rows;
-  if (n == 0) return LAMD_OK;
-  rowbase.push_back(rows);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  lamd_ctx *L;
-  int rc = pick_lane(ctx, &L);
-  if (rc != LAMD_OK) return rc;
-  u32 bits = 1;
-  while (((size_t)1 << bits) < 2 * n_cann) bits++;
-  const size_t slots = ((size_t)1 << bits) + 1;
-  // host arrays, one copy: rec_off u64[n] | start u64[nsel] | len u64[nsel] | rowbase u64[nsel + 1] | sel u32[n]
-  std::vector<u64> &pack = job->pack;
-  pack.assign(n + 3 * nsel + 1 + (n + 1) / 2, 0);
-  for (size_t i = 0; i < n; i++) pack[i] = rec_off[i];
-  if (nsel) {
-    memcpy(&pack[n], start.data(), 8 * nsel);
-    memcpy(&pack[n + nsel], mlen.data(), 8 * nsel);
-  }
-  memcpy(&pack[n + 2 * nsel], rowbase.data(), 8 * (nsel + 1));
-  memcpy(&pack[n + 3 * nsel + 1], sel.data(), 4 * n);
-  auto fail = [&](int code) {   // queued copies read this frame's vectors
-    (void)hipStreamSynchronize(L->stream);
-    if (L != ctx) ctx->err = L->err;
-    return code;
-  };
-  if ((rc = ensure(L, &L->st_host, pack.size() * 8)) != LAMD_OK) return fail(rc);
-  if ((rc = ensure(L, &L->st_ids, nsel * 33 + 16)) != LAMD_OK) return fail(rc);
-  if ((rc = ensure(L, &L->st_tab, slots * 12)) != LAMD_OK) return fail(rc);
-  if ((rc = ensure(L, &L->st_out, 3 * n + nsel + 16)) != LAMD_OK) return fail(rc);
-  if (!d_store && (rc = ensure(L, &L->st_img, len + 16)) != LAMD_OK) return fail(rc);
-  const bool timed = ctx->timing;
-  if (timed)
-    for (auto &e : L->ev_store)
-      if (!e) HIPCHK(ctx, hipEventCreate(&e));
-  hipStream_t st = L->stream;
-  const u64 *d_pack = L->st_host.as<const u64>();
-  const u64 *d_recoff = d_pack, *d_start = d_pack + n, *d_len = d_start + nsel, *d_rowbase = d_len + nsel;
-  const u32 *d_sel = (const u32 *)(d_rowbase + nsel + 1);
-  u64 *d_keys = L->st_tab.as<u64>();
-  u32 *d_vals = (u32 *)(d_keys + slots);
-  int8_t *d_pre = L->st_out.as<int8_t>(), *d_verdict = d_pre + n, *d_sigv = d_verdict + n;
-  u8 *d_aux = (u8 *)(d_sigv + nsel);
-  const u8 *img = (const u8 *)d_store;
-  if (!d_store) {
-    STCHK(hipMemcpyAsync(L->st_img.p, store, len, hipMemcpyHostToDevice, st));
-    img = L->st_img.as<const u8>();
-  }
-  STCHK(hipMemcpyAsync(L->st_host.p, pack.data(), pack.size() * 8, hipMemcpyHostToDevice, st));
-  STCHK(hipMemsetAsync(L->st_tab.p, 0xFF, slots * 12, st));
-  // slicing by 8 measured faster (0.24 ms against 0.42 ms on 750 000 records, profiles/store_audit.txt): LAMD_STORE_CRC_WAYS=8 selects it.  The
-  // default stays the variant the GPU tests have run with until they have run with the other one.
-  static const int crc_ways = [] { const char *e = getenv("LAMD_STORE_CRC_WAYS"); return e && atoi(e) == 8 ? 8 : 4; }();
-  const dim3 grid(blocks_for(n)), block(256);
-  if (timed) STCHK(hipEventRecord(L->ev_store[0], st));
-  if (crc_ways == 8) hipLaunchKernelGGL(k_store_crc<8>, grid, block, 0, st, (u32)n, img, len, d_recoff, d_pre);
-  else hipLaunchKernelGGL(k_store_crc<4>, grid, block, 0, st, (u32)n, img, len, d_recoff, d_pre);
-  if (timed) STCHK(hipEventRecord(L->ev_store[1], st));
-  hipLaunchKernelGGL(k_store_index, grid, block, 0, st, (u32)n, img, len, d_recoff, d_keys, d_vals, bits);
-  if (timed) STCHK(hipEventRecord(L->ev_store[2], st));
-  hipLaunchKernelGGL(k_store_signers, grid, block, 0, st, (u32)n, img, len, d_recoff, d_sel, (const u64 *)d_keys, (const u32 *)d_vals, bits,
-                     L->st_ids.as<u8>(), d_aux);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(L->ev_store[3], st));
-  if (nsel && (rc = gossip_device(L, nsel, img, d_start, L->st_ids.as<const u8>(), d_rowbase, (size_t)rows, d_sigv, d_len)) != LAMD_OK) return fail(rc);
-  if (timed) STCHK(hipEventRecord(L->ev_store[4], st));
-  hipLaunchKernelGGL(k_store_verdict, grid, block, 0, st, (u32)n, (const int8_t *)d_pre, d_sel, (const int8_t *)d_sigv, (const u8 *)d_aux, d_verdict);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(L->ev_store[5], st));
-  job->L = L;
-  job->n = n;
-  job->n_cann = n_cann;
-  job->img = img;
-  job->d_recoff = d_recoff;
-  job->d_keys = d_keys;
-  job->d_vals = d_vals;
-  job->bits = bits;
-  job->d_verdict = d_verdict;
-  return LAMD_OK;
-}
-// behind the synchronisation that ends a timed audit: the stage times
-static int store_audit_times(lamd_ctx *ctx, lamd_ctx *L, lamd_store_summary *summary) {
-  for (int k = 0; k < 5; k++) {
-    float ms = 0;
-    HIPCHK(ctx, hipEventElapsedTime(&ms, L->ev_store[k], L->ev_store[k + 1]));
-    summary->stage_ms[k] = ms;
-  }
-  return LAMD_OK;
-}
-extern "C" int lamd_gossip_store_audit(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t cap, uint64_t *rec_off,
-                                       int8_t *verdict, size_t *n_records, lamd_store_summary *summary) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!store || !n_records || !summary || (cap && (!rec_off || !verdict))) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  store_job job;
-  int rc = store_audit_queue(ctx, store, len, d_store, cap, rec_off, n_records, summary, &job);
-  if (rc != LAMD_OK) return rc;
-  lamd_ctx *L = job.L;
-  if (!L) { store_count_verdicts(verdict, 0, summary); return LAMD_OK; }
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(L->stream);
-    if (L != ctx) ctx->err = L->err;
-    return code;
-  };
-  STCHK(hipMemcpyAsync(verdict, job.d_verdict, job.n, hipMemcpyDeviceToHost, L->stream));
-  STCHK(hipStreamSynchronize(L->stream));
-  if (ctx->timing && (rc = store_audit_times(ctx, L, summary)) != LAMD_OK) return rc;
-  store_count_verdicts(verdict, job.n, summary);
-  return LAMD_OK;
-}
-
-// ---- gossip_store repair: the audit's stages, then keep flags, scan and copy on the same stream.  ONE wait more than the audit: the
-// verdicts, reasons, offsets and the output's length come down first (the length decides how much of the image follows).
-// lamd_gossip_store_repair and lamd_gossip_store_repair_latest differ in their keep stages alone: what lies in front of them
-// (store_rep_plan, store_repair_empty) and behind them (store_repair_finish) is one piece of code.
-struct store_rep_plan {
-  std::vector<size_t> cnt;   // the scan's levels: cnt[0] = n + 1 sizes (the last one 0), cnt[k + 1] = the tiles of level k, until one tile holds a level
-  size_t n_sums = 0, nslots = 0, upper = 0;   // all tiles' sums; slots of the node table; no output is longer than `upper`
-  u32 nbits = 1;
-  store_rep_plan(size_t n, size_t n_cann, size_t len) : cnt{n + 1} {
-    while (cnt.back() > STORE_SCAN_TILE) cnt.push_back((cnt.back() + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE);
-    for (size_t k = 1; k < cnt.size(); k++) n_sums += cnt[k];
-    while (((size_t)1 << nbits) < 4 * n_cann) nbits++;
-    nslots = (size_t)1 << nbits;
-    upper = len + STORE_REPAIR_HEAD - 1;
-  }
-};
-struct store_rep_dev {   // where the keep stages left their results, and where the output goes
-  u64 *pos, *newoff, *sums;
-  u32 *size;
-  u8 *reason, *img_out;
-  size_t dev_cap;
-};
-// a store without any record: the version byte and the uuid record
-static int store_repair_empty(lamd_ctx *ctx, const store_head &head, int8_t *verdict, lamd_store_summary *summary, uint8_t *out, void *d_out, size_t out_cap,
-                              uint64_t *out_len) {
-  store_count_verdicts(verdict, 0, summary);
-  *out_len = STORE_REPAIR_HEAD;
-  if ((out || d_out) && out_cap < STORE_REPAIR_HEAD) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
-  if (out) memcpy(out, head.b, STORE_REPAIR_HEAD);
-  if (d_out) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipMemcpy(d_out, head.b, STORE_REPAIR_HEAD, hipMemcpyHostToDevice));
-  }
-  return LAMD_OK;
-}
-// Behind the keep stages (ev_rep[0] was recorded in front of them): the scan, the copy, the two waits.  counts[r] = records with reason r;
-// stage_ms: keep, scan, copy.  *out_len and the counts are set before the output's size is checked against out_cap.
-static int store_repair_finish(lamd_ctx *ctx, const store_job &job, size_t len, const store_rep_plan &plan, const store_rep_dev &d, const store_head &head,
-                               int8_t *verdict, uint64_t *new_off, uint8_t *reason, uint8_t *out, bool want_out, size_t out_cap,
-                               lamd_store_summary *summary, uint64_t counts[8], uint64_t *out_len, double stage_ms[3]) {
-  lamd_ctx *L = job.L;
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(L->stream);
-    if (L != ctx) ctx->err = L->err;
-    return code;
-  };
-  const size_t n = job.n;
-  const std::vector<size_t> &cnt = plan.cnt;
-  const bool timed = ctx->timing;
-  hipStream_t st = L->stream;
-  int rc;
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(L->ev_rep[1], st));
-  {
-    std::vector<u64 *> lvl{d.pos};   // level k >= 1 lives in d.sums and is scanned in place
-    for (size_t k = 1, o = 0; k < cnt.size(); o += cnt[k], k++) lvl.push_back(d.sums + o);
-    const size_t top = cnt.size() - 1;
-    for (size_t k = 0; k < top; k++) {
-      if (k == 0) hipLaunchKernelGGL(k_store_scan_reduce<u32>, dim3((unsigned)cnt[1]), dim3(256), 0, st, (u64)cnt[0], (const u32 *)d.size, lvl[1]);
-      else hipLaunchKernelGGL(k_store_scan_reduce<u64>, dim3((unsigned)cnt[k + 1]), dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], lvl[k + 1]);
-    }
-    for (size_t k = top + 1; k-- > 0;) {
-      const u64 *base = k == top ? nullptr : lvl[k + 1];
-      const dim3 grid((unsigned)((cnt[k] + STORE_SCAN_TILE - 1) / STORE_SCAN_TILE));
-      if (k == 0) hipLaunchKernelGGL(k_store_scan_apply<u32>, grid, dim3(256), 0, st, (u64)cnt[0], (const u32 *)d.size, base, d.pos, (u64)n, (const u8 *)d.reason, d.newoff);
-      else hipLaunchKernelGGL(k_store_scan_apply<u64>, grid, dim3(256), 0, st, (u64)cnt[k], (const u64 *)lvl[k], base, lvl[k], (u64)0, (const u8 *)nullptr, (u64 *)nullptr);
-    }
-  }
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(L->ev_rep[2], st));
-  if (want_out && d.dev_cap) {
-    const size_t words = (3 + (plan.upper < d.dev_cap ? plan.upper : d.dev_cap)) / 4 + 1;
-    hipLaunchKernelGGL(k_store_pack, dim3((unsigned)((words + STORE_PACK_WORDS - 1) / STORE_PACK_WORDS)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff,
-                       (const u64 *)d.pos, head, d.img_out, (u64)d.dev_cap);
-    STCHK(hipGetLastError());
-  }
-  if (timed) STCHK(hipEventRecord(L->ev_rep[3], st));
-  u64 payload = 0;
-  STCHK(hipMemcpyAsync(verdict, job.d_verdict, n, hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(reason, d.reason, n, hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(new_off, d.newoff, 8 * n, hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(&payload, d.pos + n, 8, hipMemcpyDeviceToHost, st));
-  STCHK(hipStreamSynchronize(st));
-  if (timed) {
-    if ((rc = store_audit_times(ctx, L, summary)) != LAMD_OK) return rc;
-    for (int k = 0; k < 3; k++) {
-      float ms = 0;
-      STCHK(hipEventElapsedTime(&ms, L->ev_rep[k], L->ev_rep[k + 1]));
-      stage_ms[k] = ms;
-    }
-  }
-  store_count_verdicts(verdict, n, summary);
-  for (size_t i = 0; i < n; i++) counts[reason[i] & 7]++;
-  *out_len = STORE_REPAIR_HEAD + payload;
-  if (want_out && *out_len > out_cap) { ctx->err = "gossip_store repair: output buffer too small"; return LAMD_ERR_ARG; }
-  if (out) {
-    STCHK(hipMemcpyAsync(out, d.img_out, *out_len, hipMemcpyDeviceToHost, st));
-    STCHK(hipStreamSynchronize(st));
-  }
-  return LAMD_OK;
-}
-extern "C" int lamd_gossip_store_repair(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32, size_t cap,
-                                        uint64_t *rec_off, int8_t *verdict, uint64_t *new_off, uint8_t *reason, size_t *n_records, uint8_t *out,
-                                        void *d_out, size_t out_cap, lamd_store_summary *summary, lamd_store_repair_summary *repair) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!store || !uuid32 || !n_records || !summary || !repair || (cap && (!rec_off || !verdict || !new_off || !reason))) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  *repair = lamd_store_repair_summary();
-  store_job job;
-  int rc = store_audit_queue(ctx, store, len, d_store, cap, rec_off, n_records, summary, &job);
-  if (rc != LAMD_OK) return rc;
-  const store_head head = store_make_head(store[0], uuid32);
-  const bool want_out = out || d_out;
-  lamd_ctx *L = job.L;
-  if (!L) return store_repair_empty(ctx, head, verdict, summary, out, d_out, out_cap, &repair->out_len);
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(L->stream);
-    if (L != ctx) ctx->err = L->err;
-    return code;
-  };
-  const size_t n = job.n;
-  const store_rep_plan plan(n, job.n_cann, len);
-  const size_t n_sums = plan.n_sums, nslots = plan.nslots;
-  // pos u64[n + 1] | new_off u64[n] | sums u64[n_sums] | nkeys u64[nslots] | nvals u32[nslots] | size u32[n + 1] | reason u8[n]
-  if ((rc = ensure(L, &L->st_rep, 8 * (2 * n + 1 + n_sums + nslots) + 4 * (nslots + n + 1) + n + 16)) != LAMD_OK) return fail(rc);
-  if (want_out && !d_out && (rc = ensure(L, &L->st_pack, plan.upper + 16)) != LAMD_OK) return fail(rc);
-  const bool timed = ctx->timing;
-  if (timed)
-    for (auto &e : L->ev_rep)
-      if (!e) STCHK(hipEventCreate(&e));
-  hipStream_t st = L->stream;
-  u64 *d_pos = L->st_rep.as<u64>(), *d_newoff = d_pos + n + 1, *d_sums = d_newoff + n, *d_nkeys = d_sums + n_sums;
-  u32 *d_nvals = (u32 *)(d_nkeys + nslots), *d_size = d_nvals + nslots;
-  u8 *d_reason = (u8 *)(d_size + n + 1);
-  const store_rep_dev dev{d_pos, d_newoff, d_sums, d_size, d_reason, d_out ? (u8 *)d_out : L->st_pack.as<u8>(), d_out ? out_cap : plan.upper};
-  STCHK(hipMemsetAsync(d_nkeys, 0xFF, nslots * 12, st));
-  if (timed) STCHK(hipEventRecord(L->ev_rep[0], st));
-  hipLaunchKernelGGL(k_store_keep_chan, dim3(blocks_for(n)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, d_nkeys, d_nvals, plan.nbits,
-                     d_reason, d_size);
-  hipLaunchKernelGGL(k_store_keep_rest, dim3(blocks_for(n + 1)), dim3(256), 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals,
-                     job.bits, (const u64 *)d_nkeys, (const u32 *)d_nvals, plan.nbits, d_reason, d_size);
-  uint64_t counts[8] = {};
-  rc = store_repair_finish(ctx, job, len, plan, dev, head, verdict, new_off, reason, out, want_out, out_cap, summary, counts, &repair->out_len, repair->stage_ms);
-  repair->kept = counts[STORE_DROP_KEPT];
-  repair->dropped_deleted = counts[STORE_DROP_DELETED];
-  repair->dropped_verdict = counts[STORE_DROP_VERDICT];
-  repair->dropped_dependency = counts[STORE_DROP_DEPENDENCY];
-  repair->dropped_bookkeeping = counts[STORE_DROP_BOOKKEEPING];
-  return rc;
-}
-
-// ---- latest-wins repair: the same call with four keep stages (store_latest.h) in place of two
-extern "C" int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, const uint8_t *uuid32,
-                                               const lamd_store_latest_policy *policy, size_t cap, uint64_t *rec_off, int8_t *verdict, uint64_t *new_off,
-                                               uint8_t *reason, size_t *n_records, uint8_t *out, void *d_out, size_t out_cap,
-                                               lamd_store_summary *summary, lamd_store_latest_summary *latest) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!store || !uuid32 || !policy || !n_records || !summary || !latest || (cap && (!rec_off || !verdict || !new_off || !reason))) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  *latest = lamd_store_latest_summary();
-  const lamd_store_latest_policy pol = *policy;
-  store_job job;
-  int rc = store_audit_queue(ctx, store, len, d_store, cap, rec_off, n_records, summary, &job);
-  if (rc != LAMD_OK) return rc;
-  const store_head head = store_make_head(store[0], uuid32);
-  const bool want_out = out || d_out;
-  lamd_ctx *L = job.L;
-  if (!L) return store_repair_empty(ctx, head, verdict, summary, out, d_out, out_cap, &latest->out_len);
-  auto fail = [&](int code) {
-    (void)hipStreamSynchronize(L->stream);
-    if (L != ctx) ctx->err = L->err;
-    return code;
-  };
-  const size_t n = job.n;
-  const store_rep_plan plan(n, job.n_cann, len);
-  const size_t n_sums = plan.n_sums, nslots = plan.nslots;
-  // pos u64[n + 1] | new_off u64[n] | sums u64[n_sums] | latest u64[2 n] | nlatest u64[nslots] | nkeys u64[nslots] | nvals u32[nslots] | size u32[n + 1] |
-  // reason u8[n] | dying u8[n]
-  if ((rc = ensure(L, &L->st_rep, 8 * (4 * n + 1 + n_sums + 2 * nslots) + 4 * (nslots + n + 1) + 2 * n + 16)) != LAMD_OK) return fail(rc);
-  if (want_out && !d_out && (rc = ensure(L, &L->st_pack, plan.upper + 16)) != LAMD_OK) return fail(rc);
-  const bool timed = ctx->timing;
-  if (timed)
-    for (auto &e : L->ev_rep)
-      if (!e) STCHK(hipEventCreate(&e));
-  hipStream_t st = L->stream;
-  u64 *d_pos = L->st_rep.as<u64>(), *d_newoff = d_pos + n + 1, *d_sums = d_newoff + n, *d_latest = d_sums + n_sums, *d_nlatest = d_latest + 2 * n,
-      *d_nkeys = d_nlatest + nslots;
-  u32 *d_nvals = (u32 *)(d_nkeys + nslots), *d_size = d_nvals + nslots;
-  u8 *d_reason = (u8 *)(d_size + n + 1), *d_dying = d_reason + n;
-  const store_rep_dev dev{d_pos, d_newoff, d_sums, d_size, d_reason, d_out ? (u8 *)d_out : L->st_pack.as<u8>(), d_out ? out_cap : plan.upper};
-  if (timed) STCHK(hipEventRecord(L->ev_rep[0], st));
-  STCHK(hipMemsetAsync(d_latest, 0, 8 * (2 * n + nslots), st));
-  STCHK(hipMemsetAsync(d_nkeys, 0xFF, nslots * 12, st));
-  STCHK(hipMemsetAsync(d_dying, 0, n, st));
-  const dim3 grid(blocks_for(n)), block(256);
-  hipLaunchKernelGGL(k_store_latest_upd, grid, block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals, job.bits, pol, d_latest,
-                     d_dying);
-  hipLaunchKernelGGL(k_store_latest_chan, grid, block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, pol, (const u64 *)d_latest, (const u8 *)d_dying,
-                     d_nkeys, d_nvals, plan.nbits, d_reason, d_size);
-  hipLaunchKernelGGL(k_store_latest_node, grid, block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, (const u64 *)d_nkeys, (const u32 *)d_nvals,
-                     plan.nbits, pol, d_nlatest);
-  hipLaunchKernelGGL(k_store_latest_rest, dim3(blocks_for(n + 1)), block, 0, st, (u32)n, job.img, len, job.d_recoff, job.d_verdict, job.d_keys, job.d_vals,
-                     job.bits, (const u64 *)d_nkeys, (const u32 *)d_nvals, plan.nbits, pol, (const u64 *)d_latest, (const u64 *)d_nlatest, d_reason, d_size);
-  uint64_t counts[8] = {};
-  rc = store_repair_finish(ctx, job, len, plan, dev, head, verdict, new_off, reason, out, want_out, out_cap, summary, counts, &latest->out_len, latest->stage_ms);
-  latest->kept = counts[STORE_DROP_KEPT];
-  latest->dropped_deleted = counts[STORE_DROP_DELETED];
-  latest->dropped_verdict = counts[STORE_DROP_VERDICT];
-  latest->dropped_dependency = counts[STORE_DROP_DEPENDENCY];
-  latest->dropped_bookkeeping = counts[STORE_DROP_BOOKKEEPING];
-  latest->dropped_superseded = counts[STORE_DROP_SUPERSEDED];
-  latest->dropped_timestamp = counts[STORE_DROP_TIMESTAMP];
-  latest->dropped_stale = counts[STORE_DROP_STALE];
-  return rc;
-}
-
-// ---- the channel digest of a store image, and query_channel_range answered from it.  Both calls run on the context's own stream.
-struct lamd_store_digest {
-  lamd_ctx *ctx = nullptr;
-  void *mem = nullptr;        // scid u64[cap] | ts u32[2 cap] | csum u32[2 cap] | rec u32[3 cap]
-  u64 *scid = nullptr;
-  u32 *ts = nullptr, *csum = nullptr, *rec = nullptr;
-  size_t cap = 0, count = 0;  // cap = the records of the store: the sort runs over that many pairs
-};
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-extern "C" void lamd_store_digest_free(lamd_store_digest *d) {
-  if (!d) return;
-  if (d->mem) {
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipFree(d->mem);
-  }
-  delete d;
-}
-extern "C" size_t lamd_store_digest_count(const lamd_store_digest *d) { return d ? d->count : 0; }
-extern "C" int lamd_store_digest_read(const lamd_store_digest *d, size_t cap, uint64_t *scid, uint32_t *ts, uint32_t *csum, uint32_t *rec) {
-  if (!d) return LAMD_ERR_ARG;
-  lamd_ctx *ctx = d->ctx;
-  if (cap < d->count) { ctx->err = "gossip_store digest: arrays too small"; return LAMD_ERR_ARG; }
-  if (d->count == 0) return LAMD_OK;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (scid) HIPCHK(ctx, hipMemcpy(scid, d->scid, 8 * d->count, hipMemcpyDeviceToHost));
-  if (ts) HIPCHK(ctx, hipMemcpy(ts, d->ts, 8 * d->count, hipMemcpyDeviceToHost));
-  if (csum) HIPCHK(ctx, hipMemcpy(csum, d->csum, 8 * d->count, hipMemcpyDeviceToHost));
-  if (rec) HIPCHK(ctx, hipMemcpy(rec, d->rec, 12 * d->count, hipMemcpyDeviceToHost));
-  return LAMD_OK;
-}
-extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
-                                              const int8_t *verdict, lamd_store_digest **digest, lamd_store_digest_summary *summary) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (digest) *digest = nullptr;
-  if ((!store && !d_store) || !digest || !summary || (n && !rec_off)) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
-  if (n >= (size_t)STORE_NONE / 2) { ctx->err = "gossip_store digest: too many records"; return LAMD_ERR_ARG; }
-  *summary = lamd_store_digest_summary();
-  summary->records = n;
-  lamd_store_digest *D = new (std::nothrow) lamd_store_digest();
-  if (!D) return LAMD_ERR_NOMEM;
-  D->ctx = ctx;
-  D->cap = n;
-  if (n == 0) { *digest = D; return LAMD_OK; }
-  lamd_ctx *L = ctx;
-  hipStream_t st = ctx->stream;
-  auto fail = [&](int code) {   // queued copies read the caller's arrays
-    (void)hipStreamSynchronize(st);
-    lamd_store_digest_free(D);
-    return code;
-  };
-  hipError_t e0 = hipSetDevice(ctx->device);
-  if (e0 == hipSuccess) e0 = hipMalloc(&D->mem, 36 * n);
-  if (e0 != hipSuccess) { ctx->err = std::string("gossip_store digest: ") + hipGetErrorString(e0); return fail(e0 == hipErrorOutOfMemory ? LAMD_ERR_NOMEM : LAMD_ERR_HIP); }
-  D->scid = (u64 *)D->mem;
-  D->ts = (u32 *)(D->scid + n);
-  D->csum = D->ts + 2 * n;
-  D->rec = D->csum + 2 * n;
-  u32 bits = 1;
-  while (((size_t)1 << bits) < 2 * n) bits++;
-  const size_t slots = ((size_t)1 << bits) + 1;
-  size_t sort_bytes = 0;
-  STCHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 64, st));
-  // rec_off u64[n] | pair_key u64[n] | keys u64[slots] | vals u32[slots] | slot u32[2 n] | pair_val u32[n] | ann u32[n] | cnt u32[DIGEST_CNTS] | verdict i8[n] |
-  // (256-aligned) the sort's workspace
-  const size_t o_sort = align_up(8 * (2 * n + slots) + 4 * (slots + 4 * n + DIGEST_CNTS) + n, 256);
-  int rc;
-  if ((rc = ensure(ctx, &ctx->st_dig, o_sort + sort_bytes + 16)) != LAMD_OK) return fail(rc);
-  if (!d_store && (rc = ensure(ctx, &ctx->st_img, len + 16)) != LAMD_OK) return fail(rc);
-  const bool timed = ctx->timing;
-  if (timed)
-    for (auto &e : ctx->ev_dig)
-      if (!e) STCHK(hipEventCreate(&e));
-  u64 *d_recoff = ctx->st_dig.as<u64>(), *d_pkey = d_recoff + n, *d_keys = d_pkey + n;
-  u32 *d_vals = (u32 *)(d_keys + slots), *d_slot = d_vals + slots, *d_pval = d_slot + 2 * n, *d_ann = d_pval + n, *d_cnt = d_ann + n;
-  int8_t *d_verdict = verdict ? (int8_t *)(d_cnt + DIGEST_CNTS) : nullptr;
-  void *d_sort = ctx->st_dig.as<u8>() + o_sort;
-  const u8 *img = (const u8 *)d_store;
-  if (!d_store) {
-    STCHK(hipMemcpyAsync(ctx->st_img.p, store, len, hipMemcpyHostToDevice, st));
-    img = ctx->st_img.as<const u8>();
-  }
-  STCHK(hipMemcpyAsync(d_recoff, rec_off, 8 * n, hipMemcpyHostToDevice, st));
-  if (verdict) STCHK(hipMemcpyAsync(d_verdict, verdict, n, hipMemcpyHostToDevice, st));
-  STCHK(hipMemsetAsync(d_pkey, 0xFF, 8 * (n + slots) + 4 * slots, st));   // pair_key, keys, vals
-  STCHK(hipMemsetAsync(d_slot, 0, 8 * n, st));
-  STCHK(hipMemsetAsync(d_pval, 0xFF, 4 * n, st));
-  STCHK(hipMemsetAsync(d_cnt, 0, 4 * DIGEST_CNTS, st));
-  const dim3 grid(blocks_for(n)), block(256);
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[0], st));
-  hipLaunchKernelGGL(k_digest_index, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, d_keys, d_vals, bits);
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[1], st));
-  hipLaunchKernelGGL(k_digest_slots, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, (const u64 *)d_keys, (const u32 *)d_vals,
-                     bits, d_slot, d_cnt);
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[2], st));
-  hipLaunchKernelGGL(k_digest_chan, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, (const u64 *)d_keys, (const u32 *)d_vals,
-                     bits, (const u32 *)d_slot, d_pkey, d_pval, d_cnt);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[3], st));
-  STCHK(rocprim::radix_sort_pairs(d_sort, sort_bytes, (const u64 *)d_pkey, D->scid, (const u32 *)d_pval, d_ann, n, 0, 64, st));
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[4], st));
-  hipLaunchKernelGGL(k_digest_entries, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const u32 *)d_slot, (const u32 *)d_ann, (const u32 *)d_cnt, D->ts,
-                     D->csum, D->rec);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[5], st));
-  u32 cnt[DIGEST_CNTS] = {};
-  STCHK(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-  STCHK(hipStreamSynchronize(st));
-  if (timed)
-    for (int k = 0; k < 5; k++) {
-      float ms = 0;
-      STCHK(hipEventElapsedTime(&ms, ctx->ev_dig[k], ctx->ev_dig[k + 1]));
-      summary->stage_ms[k] = ms;
-    }
-  D->count = cnt[DIGEST_CNT_ENTRIES];
-  summary->entries = cnt[DIGEST_CNT_ENTRIES];
-  summary->channels = cnt[DIGEST_CNT_CHANNELS];
-  summary->channels_no_update = cnt[DIGEST_CNT_NO_UPDATE];
-  summary->updates_no_channel = cnt[DIGEST_CNT_NO_CHANNEL];
-  summary->updates_in_front = cnt[DIGEST_CNT_IN_FRONT];
-  summary->updates_short = cnt[DIGEST_CNT_SHORT];
-  *digest = D;
-  return LAMD_OK;
-}
-
-extern "C" int lamd_channel_range_reply_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, size_t nq, const uint8_t *queries,
-                                              const uint64_t *qoff, uint32_t max_encoded_bytes, int8_t *status, uint64_t *reply_first, size_t msg_cap,
-                                              uint64_t *msg_off, uint8_t *out, void *d_out, size_t out_cap, lamd_range_reply_summary *summary) {
-  if (!ctx) return LAMD_ERR_ARG;
-  if (!digest || digest->ctx != ctx || !chain_hash32 || !summary || !reply_first || (nq && (!queries || !qoff || !status)) || (msg_cap && !msg_off) ||
-      nq >= (size_t)STORE_NONE) {
-    ctx->err = "bad argument";
-    return LAMD_ERR_ARG;
-  }
-  *summary = lamd_range_reply_summary();
-  reply_first[0] = 0;
-  if (nq == 0) {
-    if (msg_cap) msg_off[0] = 0;
-    return LAMD_OK;
-  }
-  std::vector<store_range_query> qs(nq);
-  for (size_t q = 0; q < nq; q++) {
-    if (qoff[q + 1] < qoff[q]) { ctx->err = "channel_range replies: decreasing query offsets"; return LAMD_ERR_ARG; }
-    qs[q] = store_range_parse(queries + qoff[q], (size_t)(qoff[q + 1] - qoff[q]), chain_hash32, max_encoded_bytes);
-    status[q] = (int8_t)qs[q].kind;
-    (qs[q].kind == STORE_RANGE_ANSWERED ? summary->answered : qs[q].kind == STORE_RANGE_FOREIGN ? summary->foreign : summary->malformed)++;
-  }
-  lamd_ctx *L = ctx;
-  hipStream_t st = ctx->stream;
-  auto fail = [&](int code) {   // queued copies read this frame's vectors
-    (void)hipStreamSynchronize(st);
-    return code;
-  };
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const u32 count = (u32)digest->count;
-  // no query has more than count + 1 replies: the device arrays need not follow a generous msg_cap
-  const u64 most = (u64)nq * ((u64)count + 1), cap_dev = msg_cap < most ? msg_cap : most;
-  // msg_first u64[nq + 1] | byte_first u64[nq + 1] | n_bytes u64[nq] | msg_off u64[cap_dev + 1] | queries[nq] | msgs[cap_dev] | n_msgs u32[nq]
-  int rc;
-  if ((rc = ensure(ctx, &ctx->st_rng, 8 * (3 * nq + 2 + cap_dev + 1) + sizeof(store_range_query) * nq + sizeof(store_range_msg) * cap_dev + 4 * nq + 16)) != LAMD_OK)
-    return rc;
-  const bool timed = ctx->timing;
-  if (timed)
-    for (auto &e : ctx->ev_dig)
-      if (!e) HIPCHK(ctx, hipEventCreate(&e));
-  u64 *d_mfirst = ctx->st_rng.as<u64>(), *d_bfirst = d_mfirst + nq + 1, *d_nbytes = d_bfirst + nq + 1, *d_msgoff = d_nbytes + nq;
-  store_range_query *d_qs = (store_range_query *)(d_msgoff + cap_dev + 1);
-  store_range_msg *d_msgs = (store_range_msg *)(d_qs + nq);
-  u32 *d_nmsgs = (u32 *)(d_msgs + cap_dev);
-  std::vector<u64> h_first(2 * (nq + 1)), h_msgoff(cap_dev + 1);
-  const dim3 grid(blocks_for(nq)), block(256);
-  STCHK(hipMemcpyAsync(d_qs, qs.data(), sizeof(store_range_query) * nq, hipMemcpyHostToDevice, st));
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[0], st));
-  hipLaunchKernelGGL(k_range_count, grid, block, 0, st, (u32)nq, (const store_range_query *)d_qs, (const u64 *)digest->scid, count, d_nmsgs, d_nbytes);
-  hipLaunchKernelGGL(k_range_scan, dim3(1), block, 0, st, (u32)nq, (const u32 *)d_nmsgs, (const u64 *)d_nbytes, d_mfirst, d_bfirst);
-  hipLaunchKernelGGL(k_range_plan, grid, block, 0, st, (u32)nq, (const store_range_query *)d_qs, (const u64 *)digest->scid, count, (const u64 *)d_mfirst,
-                     (const u64 *)d_bfirst, (u64)cap_dev, d_msgs, d_msgoff);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[1], st));
-  STCHK(hipMemcpyAsync(h_first.data(), d_mfirst, 16 * (nq + 1), hipMemcpyDeviceToHost, st));
-  STCHK(hipMemcpyAsync(h_msgoff.data(), d_msgoff, 8 * (cap_dev + 1), hipMemcpyDeviceToHost, st));
-  STCHK(hipStreamSynchronize(st));
-  const u64 n_msgs = h_first[nq], total = h_first[2 * nq + 1];
-  summary->messages = n_msgs;
-  summary->bytes = total;
-  memcpy(reply_first, h_first.data(), 8 * (nq + 1));
-  if (n_msgs > msg_cap) { ctx->err = "channel_range replies: msg_off too small"; return LAMD_ERR_ARG; }
-  const bool want_out = out || d_out;
-  if (want_out && total > out_cap) { ctx->err = "channel_range replies: output buffer too small"; return LAMD_ERR_ARG; }
-  if (msg_off) memcpy(msg_off, h_msgoff.data(), 8 * (n_msgs + 1));
-  if (!want_out || n_msgs == 0) return LAMD_OK;
-  if (!d_out && (rc = ensure(ctx, &ctx->st_rng_out, total + 16)) != LAMD_OK) return rc;
-  u8 *d_bytes = d_out ? (u8 *)d_out : ctx->st_rng_out.as<u8>();
-  const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
-  hipLaunchKernelGGL(k_range_encode, dim3((unsigned)((words + 255) / 256)), block, 0, st, words, (const store_range_msg *)d_msgs, (const u64 *)d_msgoff, (u32)n_msgs,
-                     (const store_range_query *)d_qs, store_digest_view{digest->scid, digest->ts, digest->csum}, d_bytes, total);
-  STCHK(hipGetLastError());
-  if (timed) STCHK(hipEventRecord(ctx->ev_dig[2], st));
-  if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
-  STCHK(hipStreamSynchronize(st));
-  if (timed)
-    for (int k = 0; k < 2; k++) {
-      float ms = 0;
-      STCHK(hipEventElapsedTime(&ms, ctx->ev_dig[k], ctx->ev_dig[k + 1]));
-      summary->stage_ms[k] = ms;
-    }
-  return LAMD_OK;
-}
-#undef STCHK
 
 extern "C" int lamd_sigcheck_gossip_batch(lamd_ctx *ctx, size_t n, const uint8_t *msgs, const uint64_t *off,
                                           const uint8_t *node_ids33, int8_t *verdict) {
@@ -5474,9 +3344,7 @@ extern "C" int lamd_wait(lamd_ctx *ctx, uint8_t *ok, size_t cap, size_t *n) {
 
 // ---- device self-test: the same inline functions evaluated on the GPU and on the host (this TU's host
 // pass), stage by stage, so a miscompile / hardware difference is localised to one primitive.
-constexpr int ST_LANES = 64;
-constexpr int ST_WORDS = 512;  // output words per lane
-struct st_in { u32 a[8], b[8]; u8 hash[32], sig[64], pub33[33], pad[3]; };
+// (ST_LANES, ST_WORDS, st_in: engine_internal.h -- the debuggers of lamd_debug.hip take the same input)
 
 LAMD_HD void selftest_lane(const st_in &in, const u32 *gtable, u32 *slot, u32 *o) {
   int k = 0;
@@ -5607,331 +3475,10 @@ extern "C" int lamd_selftest(lamd_ctx *ctx, const uint8_t *hash32, const uint8_t
   return fails;
 }
 
-// ---- op-level chain debugger: device runs a dependent chain of fe_sqr / fe_mul and records raw limbs in and out of
-// every step; the host re-executes each step on the device's own inputs and reports the first disagreement.
-constexpr int CH_ITERS = 300;
-__global__ void __launch_bounds__(64) k_chain_debug(const st_in *in, u32 *out, int use_mul) {
-  const int lane = threadIdx.x;
-  fe a = fe_from_words(in[lane].a);
-  const fe b = fe_from_words(in[lane].b);
-  u32 *o = out + (size_t)lane * CH_ITERS * 18;
-#pragma unroll 1
-  for (int it = 0; it < CH_ITERS; it++) {
-    for (int i = 0; i < 9; i++) o[it * 18 + i] = a.n[i];
-    const fe r = use_mul ? fe_mul(a, b) : fe_sqr(a);
-    for (int i = 0; i < 9; i++) o[it * 18 + 9 + i] = r.n[i];
-    a = r;
-  }
-}
-extern "C" int lamd_chain_debug(lamd_ctx *ctx, int use_mul, char *report, size_t cap) {
-  if (!ctx) return LAMD_ERR_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<st_in> in(ST_LANES);
-  u64 s = 0x7654321;
-  for (int i = 0; i < ST_LANES; i++)
-    for (int j = 0; j < 8; j++) { in[i].a[j] = (u32)splitmix64(s++); in[i].b[j] = (u32)splitmix64(s++); }
-  st_in *d_in; u32 *d_out;
-  const size_t words = (size_t)ST_LANES * CH_ITERS * 18;
-  HIPCHK(ctx, hipMalloc(&d_in, sizeof(st_in) * ST_LANES));
-  HIPCHK(ctx, hipMalloc(&d_out, words * 4));
-  HIPCHK(ctx, hipMemcpy(d_in, in.data(), sizeof(st_in) * ST_LANES, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_chain_debug, dim3(1), dim3(ST_LANES), 0, ctx->stream, d_in, d_out, use_mul);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<u32> got(words);
-  HIPCHK(ctx, hipMemcpy(got.data(), d_out, words * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_in); (void)hipFree(d_out);
-  int nbad = 0;
-  std::string rep;
-  char buf[512];
-  for (int lane = 0; lane < ST_LANES; lane++) {
-    const fe b = fe_from_words(in[lane].b);
-    for (int it = 0; it < CH_ITERS; it++) {
-      const u32 *o = &got[((size_t)lane * CH_ITERS + it) * 18];
-      fe a;
-      for (int i = 0; i < 9; i++) a.n[i] = o[i];
-      const fe r = use_mul ? fe_mul(a, b) : fe_sqr(a);
-      bool bad = false;
-      for (int i = 0; i < 9; i++) bad |= r.n[i] != o[9 + i];
-      if (bad) {
-        if (nbad < 3) {
-          snprintf(buf, sizeof buf, "lane %d it %d in=[%x %x %x %x %x %x %x %x %x] dev=[%x %x %x %x %x %x %x %x %x] host=[%x %x %x %x %x %x %x %x %x]; ",
-                   lane, it, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12], o[13], o[14], o[15], o[16], o[17],
-                   r.n[0], r.n[1], r.n[2], r.n[3], r.n[4], r.n[5], r.n[6], r.n[7], r.n[8]);
-          rep += buf;
-          if (use_mul) { snprintf(buf, sizeof buf, "b=[%x %x %x %x %x %x %x %x %x]; ", b.n[0], b.n[1], b.n[2], b.n[3], b.n[4], b.n[5], b.n[6], b.n[7], b.n[8]); rep += buf; }
-        }
-        nbad++;
-      }
-    }
-  }
-  if (report && cap) { strncpy(report, rep.c_str(), cap - 1); report[cap - 1] = 0; }
-  return nbad;
-}
-
-// ---- inversion-chain debugger: every intermediate of the addition chain, device vs host
-constexpr int INV_ITEMS = 24;
-LAMD_HD void inv_debug_lane(const u32 aw[8], u32 *o) {
-  const fe a = fe_from_words(aw);
-  fe items[INV_ITEMS];
-  int k = 0;
-  const int ns[8] = {1, 2, 3, 5, 11, 22, 44, 88};
-  for (int j = 0; j < 8; j++) items[k++] = fe_sqr_n(a, ns[j]);  // 0..7
-  const fe x2 = fe_mul(fe_sqr(a), a);
-  const fe x3 = fe_mul(fe_sqr(x2), a);
-  const fe x6 = fe_mul(fe_sqr_n(x3, 3), x3);
-  const fe x9 = fe_mul(fe_sqr_n(x6, 3), x3);
-  const fe x11 = fe_mul(fe_sqr_n(x9, 2), x2);
-  const fe x22 = fe_mul(fe_sqr_n(x11, 11), x11);
-  const fe x44 = fe_mul(fe_sqr_n(x22, 22), x22);
-  const fe x88 = fe_mul(fe_sqr_n(x44, 44), x44);
-  const fe x176 = fe_mul(fe_sqr_n(x88, 88), x88);
-  const fe x220 = fe_mul(fe_sqr_n(x176, 44), x44);
-  const fe x223 = fe_mul(fe_sqr_n(x220, 3), x3);
-  items[k++] = x2; items[k++] = x3; items[k++] = x6; items[k++] = x9; items[k++] = x11; items[k++] = x22;   // 8..13
-  items[k++] = x44; items[k++] = x88; items[k++] = x176; items[k++] = x220; items[k++] = x223;              // 14..18
-  const fe_chain ch = fe_pow_chain(a);
-  items[k++] = ch.x2; items[k++] = ch.x22; items[k++] = ch.x223;                                             // 19..21
-  items[k++] = fe_inv(a);                                                                                     // 22
-  items[k++] = fe_sqrt_candidate(a);                                                                          // 23
-  for (int j = 0; j < INV_ITEMS; j++) {
-    u32 w[8];
-    fe_to_words(w, fe_normalize(items[j]));
-    for (int i = 0; i < 8; i++) o[j * 8 + i] = w[i];
-  }
-}
-__global__ void __launch_bounds__(64) k_inv_debug(const st_in *in, u32 *out) {
-  inv_debug_lane(in[threadIdx.x].a, out + threadIdx.x * INV_ITEMS * 8);
-}
-extern "C" int lamd_inv_debug(lamd_ctx *ctx, char *report, size_t cap) {
-  if (!ctx) return LAMD_ERR_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<st_in> in(ST_LANES);
-  u64 s = 0xABCDEF;
-  for (int i = 0; i < ST_LANES; i++)
-    for (int j = 0; j < 8; j++) in[i].a[j] = (u32)splitmix64(s++);
-  st_in *d_in; u32 *d_out;
-  const size_t words = (size_t)ST_LANES * INV_ITEMS * 8;
-  HIPCHK(ctx, hipMalloc(&d_in, sizeof(st_in) * ST_LANES));
-  HIPCHK(ctx, hipMalloc(&d_out, words * 4));
-  HIPCHK(ctx, hipMemcpy(d_in, in.data(), sizeof(st_in) * ST_LANES, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_inv_debug, dim3(1), dim3(ST_LANES), 0, ctx->stream, d_in, d_out);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<u32> got(words), exp(INV_ITEMS * 8);
-  HIPCHK(ctx, hipMemcpy(got.data(), d_out, words * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_in); (void)hipFree(d_out);
-  int mask = 0;
-  std::string rep;
-  for (int lane = 0; lane < ST_LANES; lane++) {
-    inv_debug_lane(in[lane].a, exp.data());
-    for (int j = 0; j < INV_ITEMS; j++)
-      if (memcmp(&exp[j * 8], &got[((size_t)lane * INV_ITEMS + j) * 8], 32)) {
-        if (!(mask & (1 << j))) {
-          rep += "item " + std::to_string(j) + " first bad at lane " + std::to_string(lane) + "; ";
-          if (rep.size() < 1500) {
-            char buf[400];
-            const u32 *g = &got[((size_t)lane * INV_ITEMS + j) * 8], *e = &exp[j * 8], *aw = in[lane].a;
-            snprintf(buf, sizeof buf, "a=%08x%08x%08x%08x%08x%08x%08x%08x dev=%08x%08x%08x%08x%08x%08x%08x%08x host=%08x%08x%08x%08x%08x%08x%08x%08x; ",
-                     aw[7], aw[6], aw[5], aw[4], aw[3], aw[2], aw[1], aw[0], g[7], g[6], g[5], g[4], g[3], g[2], g[1], g[0], e[7], e[6], e[5], e[4], e[3], e[2], e[1], e[0]);
-            rep += buf;
-          }
-        }
-        mask |= 1 << j;
-      }
-  }
-  if (report && cap) { strncpy(report, rep.c_str(), cap - 1); report[cap - 1] = 0; }
-  return mask;
-}
-
-// ---- x2 debugger: fe_mul(fe_sqr(a), a) in several code shapes, raw limbs out
-__global__ void __launch_bounds__(64) k_x2_debug(const st_in *in, u32 *out) {
-  const int lane = threadIdx.x;
-  u32 *o = out + lane * 64;
-  const fe a = fe_from_words(in[lane].a);
-  {  // A: fused, raw result
-    const fe r = fe_mul(fe_sqr(a), a);
-    for (int i = 0; i < 9; i++) o[i] = r.n[i];
-  }
-  {  // B: intermediate forced through an opaque register barrier
-    fe s2 = fe_sqr(a);
-#if defined(__HIP_DEVICE_COMPILE__)
-    for (int i = 0; i < 9; i++) asm volatile("" : "+v"(s2.n[i]));
-#endif
-    const fe r = fe_mul(s2, a);
-    for (int i = 0; i < 9; i++) o[9 + i] = s2.n[i];
-    for (int i = 0; i < 9; i++) o[18 + i] = r.n[i];
-  }
-  {  // C: fused then normalized
-    const fe r = fe_normalize(fe_mul(fe_sqr(a), a));
-    for (int i = 0; i < 9; i++) o[27 + i] = r.n[i];
-  }
-  {  // D: a*a via fe_mul, then *a
-    const fe r = fe_mul(fe_mul(a, a), a);
-    for (int i = 0; i < 9; i++) o[36 + i] = r.n[i];
-  }
-}
-extern "C" int lamd_x2_debug(lamd_ctx *ctx, char *report, size_t cap) {
-  if (!ctx) return LAMD_ERR_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  std::vector<st_in> in(ST_LANES);
-  u64 s = 0xABCDEF;
-  for (int i = 0; i < ST_LANES; i++)
-    for (int j = 0; j < 8; j++) in[i].a[j] = (u32)splitmix64(s++);
-  st_in *d_in; u32 *d_out;
-  HIPCHK(ctx, hipMalloc(&d_in, sizeof(st_in) * ST_LANES));
-  HIPCHK(ctx, hipMalloc(&d_out, ST_LANES * 64 * 4));
-  HIPCHK(ctx, hipMemcpy(d_in, in.data(), sizeof(st_in) * ST_LANES, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_x2_debug, dim3(1), dim3(ST_LANES), 0, ctx->stream, d_in, d_out);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<u32> got(ST_LANES * 64);
-  HIPCHK(ctx, hipMemcpy(got.data(), d_out, got.size() * 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_in); (void)hipFree(d_out);
-  std::string rep;
-  int mask = 0;
-  char buf[600];
-  for (int lane = 0; lane < ST_LANES; lane++) {
-    const fe a = fe_from_words(in[lane].a);
-    const fe s2 = fe_sqr(a);
-    const fe r = fe_mul(s2, a);
-    const fe rn = fe_normalize(r);
-    const fe rd = fe_mul(fe_mul(a, a), a);
-    const u32 *o = &got[lane * 64];
-    const fe *exps[5] = {&r, &s2, &r, &rn, &rd};
-    const char *names[5] = {"A_fused_raw", "B_sqr_raw", "B_mul_raw", "C_fused_norm", "D_mulmul"};
-    for (int t = 0; t < 5; t++) {
-      bool bad = false;
-      for (int i = 0; i < 9; i++) bad |= exps[t]->n[i] != o[t * 9 + i];
-      if (bad) {
-        if (!(mask & (1 << t))) {
-          const u32 *g = o + t * 9;
-          const u32 *e = exps[t]->n;
-          snprintf(buf, sizeof buf, "%s lane %d dev=[%x %x %x %x %x %x %x %x %x] host=[%x %x %x %x %x %x %x %x %x]; ", names[t], lane, g[0], g[1], g[2], g[3], g[4],
-                   g[5], g[6], g[7], g[8], e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7], e[8]);
-          rep += buf;
-        }
-        mask |= 1 << t;
-      }
-    }
-  }
-  if (report && cap) { strncpy(report, rep.c_str(), cap - 1); report[cap - 1] = 0; }
-  return mask;
-}
-
-// ---- randomised arithmetic fuzz (fuzz.h): the same inline function on the device and in this TU's host pass
-__global__ void __launch_bounds__(256) k_fuzz_field(size_t lanes, int iters, u64 seed, u64 *__restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < lanes) out[i] = fuzz_lane(seed, i, iters);
-}
-extern "C" int lamd_fuzz_field(lamd_ctx *ctx, size_t lanes, int iters, uint64_t seed, uint64_t *ops, char *report, size_t cap) {
-  if (!ctx || lanes == 0 || lanes > ((size_t)1 << 24) || iters < 1 || iters > 100000) return LAMD_ERR_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  u64 *d_out = nullptr;
-  HIPCHK(ctx, hipMalloc(&d_out, lanes * 8));
-  hipLaunchKernelGGL(k_fuzz_field, dim3(blocks_for(lanes)), dim3(256), 0, ctx->stream, lanes, iters, (u64)seed, d_out);
-  HIPCHK(ctx, hipGetLastError());
-  std::vector<u64> got(lanes);
-  HIPCHK(ctx, hipMemcpyAsync(got.data(), d_out, lanes * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d_out);
-  int nbad = 0;
-  std::string rep;
-  for (size_t i = 0; i < lanes; i++) {
-    const u64 exp = fuzz_lane(seed, i, iters);
-    if (exp != got[i]) {
-      if (nbad < 4) rep += "lane " + std::to_string(i) + " device " + std::to_string(got[i]) + " host " + std::to_string(exp) + "; ";
-      nbad++;
-    }
-  }
-  if (ops) *ops = (uint64_t)lanes * ((uint64_t)iters * FZ_OPS_PER_ITER + FZ_OPS_TAIL);
-  if (report && cap) { strncpy(report, rep.c_str(), cap - 1); report[cap - 1] = 0; }
-  return nbad;
-}
-
-// ---- diagnostic peek into the engine's device work buffers (tests / debugging only)
-// ---- the roofline's denominator, measured in the process that reports it (include/lightning_amd_debug.h lamd_debug_mul32_peak): a dependency-free
-// stream of v_mad_u64_u32 -- eight independent 64-bit accumulators per lane, the carry-out in an SGPR pair as the multiplier's columns have it --
-// on every SIMD of the chip at a given occupancy, long enough (>= min_ms per launch) for the clock governor to settle where the ecmult kernel's
-// launches (3-4 ms) run.  s_memtime / s_memrealtime deltas of one wave give the counter ratio next to it.
-#define LAMD_MAD8 "v_mad_u64_u32 %0, s[20:21], %8, %9, %0\n\tv_mad_u64_u32 %1, s[20:21], %8, %9, %1\n\tv_mad_u64_u32 %2, s[20:21], %8, %9, %2\n\t" \
-                  "v_mad_u64_u32 %3, s[20:21], %8, %9, %3\n\tv_mad_u64_u32 %4, s[20:21], %8, %9, %4\n\tv_mad_u64_u32 %5, s[20:21], %8, %9, %5\n\t" \
-                  "v_mad_u64_u32 %6, s[20:21], %8, %9, %6\n\tv_mad_u64_u32 %7, s[20:21], %8, %9, %7\n\t"
-__global__ void __launch_bounds__(256) k_mul32_peak(u32 *__restrict__ out, u32 iters, u64 *__restrict__ clocks) {
-  const u32 x = threadIdx.x * 2654435761u + 12345u + blockIdx.x, y = x ^ 0x9E3779B9u;
-  u64 a0 = x, a1 = y, a2 = x + 1, a3 = y + 1, a4 = x + 2, a5 = y + 2, a6 = x + 3, a7 = y + 3;
-  const u64 c0 = __builtin_readcyclecounter(), r0 = wall_clock64();
-  for (u32 it = 0; it < iters; it++) {
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-      asm volatile(LAMD_MAD8 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(x), "v"(y) : "s20", "s21");
-  }
-  const u64 c1 = __builtin_readcyclecounter(), r1 = wall_clock64();
-  out[blockIdx.x * blockDim.x + threadIdx.x] = (u32)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7);
-  if (blockIdx.x == 0 && threadIdx.x == 0) { clocks[0] = c1 - c0; clocks[1] = r1 - r0; }
-}
-extern "C" int lamd_debug_mul32_peak(lamd_ctx *ctx, int waves_per_simd, double min_ms, int launches, double *lane_ops_per_s, double *avg_launch_ms,
-                                     double *memtime_per_realtime) {
-  if (!ctx || waves_per_simd < 1 || waves_per_simd > 8 || launches < 1 || !lane_ops_per_s) return LAMD_ERR_ARG;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const unsigned blocks = (unsigned)ctx->prop.multiProcessorCount * (unsigned)waves_per_simd;  // 256 threads = one wave per SIMD of a CU
-  u32 *d_out = nullptr;
-  u64 *d_clk = nullptr;
-  HIPCHK(ctx, hipMalloc((void **)&d_out, (size_t)blocks * 256 * 4));
-  if (hipMalloc((void **)&d_clk, 16) != hipSuccess) { (void)hipFree(d_out); ctx->err = "hipMalloc failed"; return LAMD_ERR_NOMEM; }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = LAMD_OK;
-  auto run = [&](u32 iters, float *ms) -> bool {
-    if (hipEventRecord(e0, ctx->stream) != hipSuccess) return false;
-    hipLaunchKernelGGL(k_mul32_peak, dim3(blocks), dim3(256), 0, ctx->stream, d_out, iters, d_clk);
-    return hipEventRecord(e1, ctx->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(ms, e0, e1) == hipSuccess;
-  };
-  float ms = 0;
-  u32 iters = 2000;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || !run(200, &ms) || !run(iters, &ms)) rc = LAMD_ERR_HIP;
-  if (rc == LAMD_OK) {
-    if (min_ms <= 0) iters = 150;  // the sub-millisecond launch of the round-1 micro-benchmark, for comparison
-    else if (ms > 0) iters = (u32)((double)iters * min_ms / ms * 1.05) + 1;
-    double sum = 0, ratio = 0;
-    for (int l = 0; l < launches && rc == LAMD_OK; l++) {
-      if (!run(iters, &ms)) { rc = LAMD_ERR_HIP; break; }
-      sum += ms;
-      u64 clk[2] = {0, 0};
-      if (hipMemcpy(clk, d_clk, 16, hipMemcpyDeviceToHost) == hipSuccess && clk[1]) ratio += (double)clk[0] / (double)clk[1];
-    }
-    if (rc == LAMD_OK) {
-      const double avg = sum / launches;
-      *lane_ops_per_s = (double)blocks * 256.0 * (double)iters * 128.0 / (avg * 1e-3);
-      if (avg_launch_ms) *avg_launch_ms = avg;
-      if (memtime_per_realtime) *memtime_per_realtime = ratio / launches;
-    }
-  }
-  if (rc != LAMD_OK) ctx->err = "lamd_debug_mul32_peak: HIP error";
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(d_out);
-  (void)hipFree(d_clk);
-  return rc;
-}
-extern "C" const void *lamd_debug_gtable(lamd_ctx *ctx) { return ctx ? (const void *)ctx->gtable : nullptr; }
-extern "C" int lamd_debug_read(lamd_ctx *ctx, int which, size_t offset, size_t nbytes, void *out) {
-  if (!ctx || !out) return LAMD_ERR_ARG;
-  const lamd_ctx::key_cache &kc = ctx->cache_store;
-  const devbuf gt = {ctx->gtable, ctx->gtable ? GTABLE_BYTES : 0};   // not a devbuf of the context: the table is shared by the device's engines
-  const devbuf *bufs[] = {&ctx->recs, &ctx->keyok, &ctx->kd_rep, &ctx->kd_uid, &ctx->row_ent, &ctx->kd_uniq, &ctx->hk[0].keyok, &ctx->hk[0].qwords, &kc.pool7,
-                          &gt, &kc.pool10, &kc.ents};
-  if (which < 0 || which >= (int)(sizeof(bufs) / sizeof(bufs[0])) || !bufs[which]->p || offset > bufs[which]->cap || nbytes > bufs[which]->cap - offset) {
-    ctx->err = "debug_read: no such buffer / out of range";
-    return LAMD_ERR_ARG;
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipMemcpy(out, (const u8 *)bufs[which]->p + offset, nbytes, hipMemcpyDeviceToHost));
-  return LAMD_OK;
-}
-
 // ---- audit of the static G table (table_audit.h): one thread per entry of [first, first + count); a bad entry bumps the count, competes for the
 // lowest (index << 8 | reason) and, while there is room, leaves its (index, reason) pair in the report list
+// (kept in this unit, like lamd_selftest: it audits the table this unit's k_gtable_build wrote, and with k_gtable_audit compiled elsewhere the ecmult
+// kernels above came out with another register allocation -- profiles/engine_split_equivalence.txt)
 struct gt_audit_dev {
   unsigned long long lowest;   // (index << 8 | reason) of the lowest bad entry; all ones = none
   u32 bad;

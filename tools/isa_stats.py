@@ -11,12 +11,23 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lightning_amd", "liblightning_amd.so")
 pat = [a for a in sys.argv[1:] if not a.endswith(".so")]
+asm = notes = ""
 with tempfile.TemporaryDirectory() as td:
-    fat, co = os.path.join(td, "fat.bin"), os.path.join(td, "dev.co")
+    fat = os.path.join(td, "fat.bin")
     subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat])
-    subprocess.check_call([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    asm = subprocess.check_output([LLVM + "/llvm-objdump", "-d", co]).decode()
-    notes = subprocess.check_output([LLVM + "/llvm-readelf", "--notes", co]).decode()
+    # one offload bundle per translation unit with device code, one behind the other: the bundler reads the first of a file, so each goes into a file of its own
+    with open(fat, "rb") as f:
+        blob = f.read()
+    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)]
+    for k, at in enumerate(starts):
+        one, co = os.path.join(td, "fat%d.bin" % k), os.path.join(td, "dev%d.co" % k)
+        with open(one, "wb") as f:
+            f.write(blob[at:starts[k + 1] if k + 1 < len(starts) else len(blob)])
+        subprocess.check_call([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + one, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        if os.path.getsize(co) == 0:
+            continue
+        asm += subprocess.check_output([LLVM + "/llvm-objdump", "-d", co]).decode()
+        notes += subprocess.check_output([LLVM + "/llvm-readelf", "--notes", co]).decode()
 meta = {}
 for m in re.finditer(r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_count:\s+(\d+).*?\.vgpr_count:\s+(\d+)", notes, re.S):
     meta[m.group(1)] = (int(m.group(4)), int(m.group(3)), int(m.group(2)))
