@@ -557,16 +557,19 @@ int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *store, size_t 
  * The entries are SORTED ASCENDING BY SCID.  That is the one deliberate difference from the reference, which since it dropped its uintmap
  * emits channels in gossmap index order (:593-596) although BOLT #7 requires ascending short_channel_ids and its own split at block
  * boundaries assumes them: tests/golden/gossip_store_mesh_3x3.bin, written by the reference, holds its channels out of order.
+ *   BARE     the scids of the channels WITHOUT any slot set, ascending: gossmap_find_chan finds these too, so the comparison of peers'
+ *            replies (below) must know them; the replies never list them.  Their number is channels_no_update.
  * Launches, one stream, no host wait between them: k_digest_index (scid index), k_digest_slots (a 32-bit atomicMax of index + 1 per
- * slot), k_digest_chan (channels and compaction of (scid, announcement) pairs), rocPRIM's radix sort of the pairs, k_digest_entries
- * (timestamps and checksums, written in sorted order).  The call waits once, at its end, for the counters below.
+ * slot), k_digest_chan (channels, compaction of (scid, announcement) pairs and of the bare scids), rocPRIM's radix sorts of the pairs
+ * and of the bare scids (both inside the stage "sort"), k_digest_entries (timestamps and checksums, written in sorted order).  The call
+ * waits once, at its end, for the counters below.
  * The digest lives on the device until lamd_store_digest_free (before lamd_shutdown of its context); it does not refer to the image. */
 typedef struct lamd_store_digest lamd_store_digest;
 typedef struct {
 	uint64_t records;             /* n */
 	uint64_t channels;            /* channels seen */
 	uint64_t entries;             /* ... of them with at least one update: the digest's count */
-	uint64_t channels_no_update;  /* ... and without any */
+	uint64_t channels_no_update;  /* ... and without any: the bare list's count */
 	uint64_t updates_no_channel, updates_in_front, updates_short;   /* counting 258 records ignored, by reason */
 	double stage_ms[5];           /* with lamd_set_timing: index, slots, channels, sort, entries */
 } lamd_store_digest_summary;
@@ -576,6 +579,9 @@ void lamd_store_digest_free(lamd_store_digest *digest);
 size_t lamd_store_digest_count(const lamd_store_digest *digest);
 /* copies the digest back: scid[cap], ts[2 * cap], csum[2 * cap], rec[3 * cap] (any may be NULL); cap < count: LAMD_ERR_ARG */
 int lamd_store_digest_read(const lamd_store_digest *digest, size_t cap, uint64_t *scid, uint32_t *ts, uint32_t *csum, uint32_t *rec);
+/* the channels without an update: their number, and their scids copied back, ascending; cap < count: LAMD_ERR_ARG */
+size_t lamd_store_digest_bare_count(const lamd_store_digest *digest);
+int lamd_store_digest_read_bare(const lamd_store_digest *digest, size_t cap, uint64_t *scid);
 
 /* THE REPLIES.  Query q is the raw wire message queries + qoff[q] .. qoff[q + 1]: be16 263 | chain_hash 32 | be32 first_blocknum | be32
  * number_of_blocks | TLV stream; TLV 1 = query_option, a bigsize, bit 0 asks for timestamps, bit 1 for checksums, other bits are ignored.
@@ -619,6 +625,61 @@ typedef struct {
 int lamd_channel_range_reply_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, size_t nq, const uint8_t *queries,
 				   const uint64_t *qoff, uint32_t max_encoded_bytes, int8_t *status, uint64_t *reply_first, size_t msg_cap,
 				   uint64_t *msg_off, uint8_t *out, void *d_out, size_t out_cap, lamd_range_reply_summary *summary);
+
+/* THE COMPARISON: what the seeker does with a peer's reply_channel_range messages -- handle_reply_channel_range() (gossipd/queries.c:183-359)
+ * feeding process_scid_probe() (gossipd/seeker.c:708-735) -- for a batch of raw messages from any number of peers, against the digest.
+ * Message i is the bytes msgs + moff[i] .. moff[i + 1] (the call reads msgs[0, moff[n])): be16 264 | chain_hash 32 | be32 first_blocknum |
+ * be32 number_of_blocks | u8 sync_complete | be16 len | encoded_short_ids | TLV stream (1: encoding_type + encoded_timestamps, 3: checksums).
+ * STATUS, parsed on the host, the checks in the reference's order, the first failure decides:
+ *   -1  not a reply_channel_range: shorter than 45 bytes, type not 264, len past the end, a TLV stream that breaks fromwire_tlv's rules
+ *       (ascending types, minimal bigsize, unknown even type), TLV 1 of length 0, TLV 3 of a length that is no multiple of 8 (:197-203)
+ *    1  chain_hash is not chain_hash32 (:205-209)
+ *    2  first_blocknum + number_of_blocks overflows 32 bits (:218-222)
+ *    3  encoded_short_ids does not decode: len 0, first byte not 0 (zlib is gone, common/decode_array.c:26-42), (len - 1) % 8 != 0 (:224-229)
+ *    4  only with want_first[n] / want_end[n], the peer's outstanding query (range_first_blocknum, exclusive range_end_blocknum):
+ *       first + number <= want_first or first >= want_end (:257-265)
+ *    5  TLV 1: encoding_type not 0, or (length - 1) % 8 != 0 (:153-157, decode_array.c:84-113)
+ *    6  the number of timestamp pairs is not the number of scids (:158-163)
+ *    0  accepted; len == 1 is accepted with no entries.  TLV 3 is validated as above and otherwise ignored.
+ *   "reply without query" (:211-215) and the sync_complete / block tally (:290-358) are per-peer protocol state: the caller's.
+ * CLASS of every entry of every accepted message (scid; t1, t2 = its timestamps, (0, 0) without TLV 1 -- zero_ts, :150):
+ *   scid is digest entry j:          flags = (t1 > ts[j][0] ? 2 : 0) | (t2 > ts[j][1] ? 4 : 0)   (SCID_QF_UPDATE1 / 2; an unset slot is 0 in
+ *                                    the digest, so this is want_update()'s `timestamp != 0` there, seeker.c:642-650)
+ *   else scid is in the bare list:   the same with both of our timestamps 0
+ *   else:                            unknown
+ *   flags == 0: nothing to do.  per_msg[3 * n]: entries, unknown entries, stale entries (flags != 0) of each message, BEFORE merging
+ *   (what peer_supplied_query_response and set_preferred_peer need); a rejected message has 0, 0, 0.
+ * MERGE  unknown_scid: the unknown scids ascending, each once (uintmap_add refuses duplicates, :700).  stale_scid / stale_flags: the
+ *   stale scids ascending, each once, with the OR of the flags of all its entries (*stale |= query_flag, :688).  Neither depends on the
+ *   order of the messages.  DELIBERATE DIFFERENCE: the reference stops adding unknown scids once it holds more than 10 000 (:696), in
+ *   arrival order; this call returns all of them and reports the counts -- a bounded map is the caller's policy, and arrival order means
+ *   nothing in a batch.
+ * QUERIES  the query_short_channel_ids messages (queries.c:46-139, wire/peer_wire.csv:382-389) for the unknown list first, max_unknown
+ *   scids each except the last (0: 8000, seeker.c:297), then for the stale list, max_stale each (0: 7000, :382); a value above its
+ *   default is LAMD_ERR_ARG; an empty list gives no message.  unknown: be16 261 | chain_hash32 | be16 1 + 8k | 0x00 | k be64 scids
+ *   (37 + 8k bytes); stale: the same, then 0x01 | bigsize 1 + k | 0x00 | k flag bytes.  Message j is out + msg_off[j] .. msg_off[j + 1],
+ *   the first summary->unknown_messages of them are those of the unknown list.  The bytes go to out (host), d_out (device, any
+ *   alignment), or neither.
+ * SIZES  scid_cap must hold each list, msg_cap the messages, out_cap the bytes (when out or d_out is given).  One too small:
+ *   LAMD_ERR_ARG with summary, status and per_msg filled in and nothing written to the lists, msg_off, out or d_out.  All caps 0: the
+ *   sizes alone (LAMD_OK when there is nothing to hold).
+ * Device work, on the context's stream: k_cmp_classify (one lane per entry: its message by bisection in the prefix sums, two binary
+ * searches, compaction with one atomic per wave), k_cmp_per_msg (one wave per message, no atomics), rocPRIM's radix sorts, then per list
+ * k_cmp_heads, an inclusive scan and k_cmp_merge; k_cmp_plan (message offsets); k_cmp_encode, one aligned 32-bit word of the output per
+ * lane.  The host waits once for counts and sizes and once for the lists and the bytes.  Limits: n and the sum of the entries below
+ * UINT32_MAX, moff non-decreasing, the digest built by this context. */
+typedef struct {
+	uint64_t by_status[8];   /* messages: [0] accepted, [1..6] statuses 1..6, [7] malformed */
+	uint64_t entries, entries_unknown, entries_stale;   /* before merging */
+	uint64_t unknown, stale; /* after merging: what scid_cap must hold (each list) */
+	uint64_t unknown_messages, messages, bytes;   /* what msg_cap and out_cap must hold */
+	double stage_ms[4];      /* with lamd_set_timing: classify, merge, plan, encode */
+} lamd_range_compare_summary;
+int lamd_channel_range_compare_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, size_t n, const uint8_t *msgs,
+				     const uint64_t *moff, const uint32_t *want_first, const uint32_t *want_end, uint32_t max_unknown,
+				     uint32_t max_stale, int8_t *status, uint32_t *per_msg, size_t scid_cap, uint64_t *unknown_scid,
+				     uint64_t *stale_scid, uint8_t *stale_flags, size_t msg_cap, uint64_t *msg_off, uint8_t *out, void *d_out,
+				     size_t out_cap, lamd_range_compare_summary *summary);
 
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are

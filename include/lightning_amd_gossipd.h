@@ -22,8 +22,9 @@
  * channel_updates and node_announcements, the txout-failure set, and an append-only store (records with timestamps,
  * deletions marked) together with the byte image of the gossip_store FILE those records make (common/gossip_store.h:15-59), pruning
  * (prune_network) and dying / spent channels (channel_spent, new_block).  What is not: compaction, the seeker, local (known_amount)
- * announcements, and the peers' queries (query_channel_range is answered from a store image by lamd_channel_range_reply_batch,
- * include/lightning_amd.h; query_short_channel_ids and gossip_timestamp_filter are not built) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
+ * announcements, and the peers' queries (query_channel_range is answered from a store image by lamd_channel_range_reply_batch and the
+ * seeker's comparison of peers' reply_channel_range with the store is lamd_channel_range_compare_batch, include/lightning_amd.h; the
+ * query_short_channel_ids responder and gossip_timestamp_filter are not built) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
  * append to / delete from / re-flag the store) and it does the I/O.
  *
  * Everything observable is reported through the event callback, in the order the reference would produce it; texts

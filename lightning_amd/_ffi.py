@@ -65,6 +65,13 @@ class LamdRangeReplySummary(ctypes.Structure):
                 ("bytes", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 2)]
 
 
+class LamdRangeCompareSummary(ctypes.Structure):
+    """lamd_range_compare_summary (include/lightning_amd.h): what lamd_channel_range_compare_batch reports about a batch of peers' replies"""
+    _fields_ = [("by_status", ctypes.c_uint64 * 8), ("entries", ctypes.c_uint64), ("entries_unknown", ctypes.c_uint64), ("entries_stale", ctypes.c_uint64),
+                ("unknown", ctypes.c_uint64), ("stale", ctypes.c_uint64), ("unknown_messages", ctypes.c_uint64), ("messages", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 4)]
+
+
 class LamdGtableAuditResult(ctypes.Structure):
     """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
     _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
@@ -123,6 +130,11 @@ SYMBOLS = {
     "lamd_store_digest_free": (None, [ctypes.c_void_p]),
     "lamd_store_digest_count": (c_sz, [ctypes.c_void_p]),
     "lamd_store_digest_read": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p]),
+    "lamd_store_digest_bare_count": (c_sz, [ctypes.c_void_p]),
+    "lamd_store_digest_read_bare": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p]),
+    "lamd_channel_range_compare_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_uint32, ctypes.c_uint32,
+                                                        c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, ctypes.c_void_p, c_sz,
+                                                        ctypes.POINTER(LamdRangeCompareSummary)]),
     "lamd_channel_range_reply_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
                                                       ctypes.c_void_p, c_sz, ctypes.POINTER(LamdRangeReplySummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),

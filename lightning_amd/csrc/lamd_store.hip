@@ -1,10 +1,12 @@
-// liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest and channel-range replies
+// liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies and the comparison of peers' replies
 #include "engine_internal.h"
 #include "store_audit.h"
 #include "store_repair.h"
 #include "store_latest.h"
 #include "store_digest.h"
+#include "store_compare.h"
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <memory>
 
 // ---- gossip_store audit (lamd_gossip_store_audit; per-record logic in store_audit.h).  One lane per record throughout.
@@ -222,10 +224,12 @@ __global__ void __launch_bounds__(256) k_digest_slots(u32 n, const u8 *__restric
 }
 // the channels with an update, compacted in any order as (scid, announcement index) pairs: pair_key / pair_val hold n pairs preset to
 // all-ones bytes, so that behind the cnt[DIGEST_CNT_ENTRIES] real pairs the largest key stands -- a stable sort of all n pairs leaves the
-// real ones in front, the scid of that value included
+// real ones in front, the scid of that value included.  The channels without an update: their scids alone, compacted the same way into bare_key
+// (n keys preset to all-ones bytes; cnt[DIGEST_CNT_NO_UPDATE] is their allocator and so their count).
 __global__ void __launch_bounds__(256) k_digest_chan(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
                                                      const int8_t *__restrict__ verdict, const u64 *__restrict__ keys, const u32 *__restrict__ vals,
-                                                     u32 bits, const u32 *__restrict__ slot, u64 *__restrict__ pair_key, u32 *__restrict__ pair_val, u32 *cnt) {
+                                                     u32 bits, const u32 *__restrict__ slot, u64 *__restrict__ pair_key, u32 *__restrict__ pair_val, u64 *__restrict__ bare_key,
+                                                     u32 *cnt) {
   const u32 i = blockIdx.x * 256 + threadIdx.x;
   u64 scid = 0;
   const u32 c = i < n ? store_digest_chan_one(store, store_len, rec_off, verdict, i, keys, vals, bits, slot, &scid) : 0u;
@@ -234,8 +238,9 @@ __global__ void __launch_bounds__(256) k_digest_chan(u32 n, const u8 *__restrict
     pair_key[e] = scid;
     pair_val[e] = i;
   }
+  const u32 b = wave_alloc(&cnt[DIGEST_CNT_NO_UPDATE], c == 2, 0, nullptr);
+  if (c == 2 && b < n) bare_key[b] = scid;
   wave_count(&cnt[DIGEST_CNT_CHANNELS], c != 0);
-  wave_count(&cnt[DIGEST_CNT_NO_UPDATE], c == 2);
 }
 // entry j of the sorted digest, j < cnt[DIGEST_CNT_ENTRIES] (the grid covers n): ann[j] = its announcement.  The CRC tables as in k_store_crc.
 __global__ void __launch_bounds__(256) k_digest_entries(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
@@ -705,10 +710,10 @@ extern "C" int lamd_gossip_store_repair_latest(lamd_ctx *ctx, const uint8_t *sto
 // ---- the channel digest of a store image, and query_channel_range answered from it.  Both calls run on the context's own stream.
 struct lamd_store_digest {
   lamd_ctx *ctx = nullptr;
-  void *mem = nullptr;        // scid u64[cap] | ts u32[2 cap] | csum u32[2 cap] | rec u32[3 cap]
-  u64 *scid = nullptr;
+  void *mem = nullptr;        // scid u64[cap] | bare u64[cap] | ts u32[2 cap] | csum u32[2 cap] | rec u32[3 cap]
+  u64 *scid = nullptr, *bare = nullptr;   // bare: the scids of the channels without an update, ascending
   u32 *ts = nullptr, *csum = nullptr, *rec = nullptr;
-  size_t cap = 0, count = 0;  // cap = the records of the store: the sort runs over that many pairs
+  size_t cap = 0, count = 0, nbare = 0;   // cap = the records of the store: the sorts run over that many pairs / keys
 };
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 extern "C" void lamd_store_digest_free(lamd_store_digest *d) {
@@ -732,6 +737,16 @@ extern "C" int lamd_store_digest_read(const lamd_store_digest *d, size_t cap, ui
   if (rec) HIPCHK(ctx, hipMemcpy(rec, d->rec, 12 * d->count, hipMemcpyDeviceToHost));
   return LAMD_OK;
 }
+extern "C" size_t lamd_store_digest_bare_count(const lamd_store_digest *d) { return d ? d->nbare : 0; }
+extern "C" int lamd_store_digest_read_bare(const lamd_store_digest *d, size_t cap, uint64_t *scid) {
+  if (!d) return LAMD_ERR_ARG;
+  lamd_ctx *ctx = d->ctx;
+  if (cap < d->nbare || (d->nbare && !scid)) { ctx->err = "gossip_store digest: array too small"; return LAMD_ERR_ARG; }
+  if (d->nbare == 0) return LAMD_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpy(scid, d->bare, 8 * d->nbare, hipMemcpyDeviceToHost));
+  return LAMD_OK;
+}
 extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
                                               const int8_t *verdict, lamd_store_digest **digest, lamd_store_digest_summary *summary) {
   if (!ctx) return LAMD_ERR_ARG;
@@ -749,29 +764,32 @@ extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *stor
   lamd_ctx *L = ctx;
   hipStream_t st = ctx->stream;
   hipError_t e0 = hipSetDevice(ctx->device);
-  if (e0 == hipSuccess) e0 = hipMalloc(&D->mem, 36 * n);
+  if (e0 == hipSuccess) e0 = hipMalloc(&D->mem, 44 * n);
   if (e0 != hipSuccess) {
     ctx->err = std::string("gossip_store digest: ") + hipGetErrorString(e0);
     return drain_fail(ctx, L, e0 == hipErrorOutOfMemory ? LAMD_ERR_NOMEM : LAMD_ERR_HIP);
   }
   D->scid = (u64 *)D->mem;
-  D->ts = (u32 *)(D->scid + n);
+  D->bare = D->scid + n;
+  D->ts = (u32 *)(D->bare + n);
   D->csum = D->ts + 2 * n;
   D->rec = D->csum + 2 * n;
   u32 bits = 1;
   while (((size_t)1 << bits) < 2 * n) bits++;
   const size_t slots = ((size_t)1 << bits) + 1;
-  size_t sort_bytes = 0;
+  size_t sort_bytes = 0, sort_bare_bytes = 0;
   STCHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 64, st));
-  // rec_off u64[n] | pair_key u64[n] | keys u64[slots] | vals u32[slots] | slot u32[2 n] | pair_val u32[n] | ann u32[n] | cnt u32[DIGEST_CNTS] | verdict i8[n] |
-  // (256-aligned) the sort's workspace
-  const size_t o_sort = align_up(8 * (2 * n + slots) + 4 * (slots + 4 * n + DIGEST_CNTS) + n, 256);
+  STCHK(rocprim::radix_sort_keys(nullptr, sort_bare_bytes, (const u64 *)nullptr, (u64 *)nullptr, n, 0, 64, st));
+  if (sort_bare_bytes > sort_bytes) sort_bytes = sort_bare_bytes;   // the two sorts follow each other in one workspace
+  // rec_off u64[n] | pair_key u64[n] | bare_key u64[n] | keys u64[slots] | vals u32[slots] | slot u32[2 n] | pair_val u32[n] | ann u32[n] | cnt u32[DIGEST_CNTS] |
+  // verdict i8[n] | (256-aligned) the sorts' workspace
+  const size_t o_sort = align_up(8 * (3 * n + slots) + 4 * (slots + 4 * n + DIGEST_CNTS) + n, 256);
   int rc;
   if ((rc = ensure(ctx, &ctx->store.dig, o_sort + sort_bytes + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
   if (!d_store && (rc = ensure(ctx, &ctx->store.img, len + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
   const bool timed = ctx->timing;
   if (timed) STCHK(ctx->store.t_dig.create());
-  u64 *d_recoff = ctx->store.dig.as<u64>(), *d_pkey = d_recoff + n, *d_keys = d_pkey + n;
+  u64 *d_recoff = ctx->store.dig.as<u64>(), *d_pkey = d_recoff + n, *d_bkey = d_pkey + n, *d_keys = d_bkey + n;
   u32 *d_vals = (u32 *)(d_keys + slots), *d_slot = d_vals + slots, *d_pval = d_slot + 2 * n, *d_ann = d_pval + n, *d_cnt = d_ann + n;
   int8_t *d_verdict = verdict ? (int8_t *)(d_cnt + DIGEST_CNTS) : nullptr;
   void *d_sort = ctx->store.dig.as<u8>() + o_sort;
@@ -782,7 +800,7 @@ extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *stor
   }
   STCHK(hipMemcpyAsync(d_recoff, rec_off, 8 * n, hipMemcpyHostToDevice, st));
   if (verdict) STCHK(hipMemcpyAsync(d_verdict, verdict, n, hipMemcpyHostToDevice, st));
-  STCHK(hipMemsetAsync(d_pkey, 0xFF, 8 * (n + slots) + 4 * slots, st));   // pair_key, keys, vals
+  STCHK(hipMemsetAsync(d_pkey, 0xFF, 8 * (2 * n + slots) + 4 * slots, st));   // pair_key, bare_key, keys, vals
   STCHK(hipMemsetAsync(d_slot, 0, 8 * n, st));
   STCHK(hipMemsetAsync(d_pval, 0xFF, 4 * n, st));
   STCHK(hipMemsetAsync(d_cnt, 0, 4 * DIGEST_CNTS, st));
@@ -794,10 +812,11 @@ extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *stor
                      bits, d_slot, d_cnt);
   if (timed) STCHK(ctx->store.t_dig.record(2, st));
   hipLaunchKernelGGL(k_digest_chan, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const int8_t *)d_verdict, (const u64 *)d_keys, (const u32 *)d_vals,
-                     bits, (const u32 *)d_slot, d_pkey, d_pval, d_cnt);
+                     bits, (const u32 *)d_slot, d_pkey, d_pval, d_bkey, d_cnt);
   STCHK(hipGetLastError());
   if (timed) STCHK(ctx->store.t_dig.record(3, st));
   STCHK(rocprim::radix_sort_pairs(d_sort, sort_bytes, (const u64 *)d_pkey, D->scid, (const u32 *)d_pval, d_ann, n, 0, 64, st));
+  STCHK(rocprim::radix_sort_keys(d_sort, sort_bytes, (const u64 *)d_bkey, D->bare, n, 0, 64, st));
   if (timed) STCHK(ctx->store.t_dig.record(4, st));
   hipLaunchKernelGGL(k_digest_entries, grid, block, 0, st, (u32)n, img, len, (const u64 *)d_recoff, (const u32 *)d_slot, (const u32 *)d_ann, (const u32 *)d_cnt, D->ts,
                      D->csum, D->rec);
@@ -808,6 +827,7 @@ extern "C" int lamd_gossip_store_digest_build(lamd_ctx *ctx, const uint8_t *stor
   STCHK(hipStreamSynchronize(st));
   if (timed) STCHK(ctx->store.t_dig.read(5, summary->stage_ms));
   D->count = cnt[DIGEST_CNT_ENTRIES];
+  D->nbare = cnt[DIGEST_CNT_NO_UPDATE];
   summary->entries = cnt[DIGEST_CNT_ENTRIES];
   summary->channels = cnt[DIGEST_CNT_CHANNELS];
   summary->channels_no_update = cnt[DIGEST_CNT_NO_UPDATE];
@@ -891,3 +911,233 @@ extern "C" int lamd_channel_range_reply_batch(lamd_ctx *ctx, const lamd_store_di
   return LAMD_OK;
 }
 
+
+// ---- peers' reply_channel_range compared with the digest (lamd_channel_range_compare_batch; per-message, per-entry and per-word logic in
+// store_compare.h).  cnt: CMP_CNT_* words, all 0; the two lists' allocators take one atomic per wave.
+enum { CMP_CNT_UNKNOWN = 0, CMP_CNT_STALE = 1, CMP_CNT_UNKNOWN_MERGED = 2, CMP_CNT_STALE_MERGED = 3, CMP_CNTS = 4 };
+// k_cmp_classify: one lane per entry of the accepted messages; ent_first[n_msgs + 1]: the prefix sums of their entry counts.  cls[e] = the class;
+// the unknown scids and the stale (scid, flags) pairs are compacted in any order (E slots each, the keys preset to all-ones bytes as in k_digest_chan).
+__global__ void __launch_bounds__(256) k_cmp_classify(u32 E, const u8 *__restrict__ bytes, const store_cmp_msg *__restrict__ pm, const u64 *__restrict__ ent_first,
+                                                      u32 n_msgs, store_cmp_digest d, u8 *__restrict__ cls, u64 *__restrict__ unk_key,
+                                                      u64 *__restrict__ stale_key, u32 *__restrict__ stale_val, u32 *cnt) {
+  const u32 e = blockIdx.x * 256 + threadIdx.x;
+  u64 scid = 0;
+  u32 c = STORE_CMP_NOTHING;
+  if (e < E) {
+    const u32 i = store_range_locate(ent_first, n_msgs, e);
+    c = store_cmp_entry(bytes, pm[i], (u32)(e - ent_first[i]), d, &scid);
+    cls[e] = (u8)c;
+  }
+  const u32 pu = wave_alloc(&cnt[CMP_CNT_UNKNOWN], c == STORE_CMP_UNKNOWN, 0, nullptr), ps = wave_alloc(&cnt[CMP_CNT_STALE], c > STORE_CMP_UNKNOWN, 0, nullptr);
+  if (c == STORE_CMP_UNKNOWN && pu < E) unk_key[pu] = scid;
+  if (c > STORE_CMP_UNKNOWN && ps < E) {
+    stale_key[ps] = scid;
+    stale_val[ps] = c;
+  }
+}
+// k_cmp_per_msg: one WAVE per message sums the classes of its entries: per_msg[3 i ..] = entries, unknown, stale.  No atomics.
+__global__ void __launch_bounds__(256) k_cmp_per_msg(u32 n_msgs, const u64 *__restrict__ ent_first, const u8 *__restrict__ cls, u32 *__restrict__ per_msg) {
+  const u32 i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (i >= n_msgs) return;   // (the whole wave)
+  const u64 a = ent_first[i], b = ent_first[i + 1];
+  u32 u = 0, s = 0;
+  for (u64 e = a + lane; e < b; e += 64) {
+    const u32 c = cls[e];
+    u += c == STORE_CMP_UNKNOWN;
+    s += c > STORE_CMP_UNKNOWN;
+  }
+  for (int o = 32; o; o >>= 1) {
+    u += __shfl_down(u, o);
+    s += __shfl_down(s, o);
+  }
+  if (lane == 0) {
+    per_msg[3 * (size_t)i] = (u32)(b - a);
+    per_msg[3 * (size_t)i + 1] = u;
+    per_msg[3 * (size_t)i + 2] = s;
+  }
+}
+// The merge of one sorted list of *count real elements (the pads behind them are not looked at): k_cmp_heads marks where a run of equal
+// scids opens, rocPRIM's inclusive scan numbers the runs, k_cmp_merge writes run r's scid to out_key[r] and ORs its elements' flags into
+// out_val[r] (preset to 0; nullptr for the unknown list) -- OR does not care in which order the lanes arrive.
+__global__ void __launch_bounds__(256) k_cmp_heads(u32 E, const u64 *__restrict__ key, const u32 *__restrict__ count, u32 *__restrict__ head) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= E) return;
+  const u32 c = *count < E ? *count : E;
+  head[j] = j < c && store_cmp_head(key, j);
+}
+__global__ void __launch_bounds__(256) k_cmp_merge(u32 E, const u64 *__restrict__ key, const u32 *__restrict__ val, const u32 *__restrict__ count,
+                                                   const u32 *__restrict__ pos, u64 *__restrict__ out_key, u32 *out_val) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  const u32 c = *count < E ? *count : E;
+  if (j >= c) return;
+  const u32 r = pos[j] - 1;
+  if (store_cmp_head(key, j)) out_key[r] = key[j];
+  if (out_val) atomicOr(&out_val[r], val[j]);
+}
+// k_cmp_plan: the merged lists' lengths into cnt, and the offset of every message and of the end (msg_off[0 .. messages]; the grid covers max_msgs + 1)
+__global__ void __launch_bounds__(256) k_cmp_plan(u32 E, u32 max_msgs, u32 max_unknown, u32 max_stale, const u32 *__restrict__ pos_unknown,
+                                                  const u32 *__restrict__ pos_stale, u32 *cnt, u64 *__restrict__ msg_off) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  const u32 cu = cnt[CMP_CNT_UNKNOWN] < E ? cnt[CMP_CNT_UNKNOWN] : E, cs = cnt[CMP_CNT_STALE] < E ? cnt[CMP_CNT_STALE] : E;
+  store_cmp_layout y;
+  y.unknown = cu ? pos_unknown[cu - 1] : 0;
+  y.stale = cs ? pos_stale[cs - 1] : 0;
+  y.max_unknown = max_unknown;
+  y.max_stale = max_stale;
+  if (j == 0) {
+    cnt[CMP_CNT_UNKNOWN_MERGED] = y.unknown;
+    cnt[CMP_CNT_STALE_MERGED] = y.stale;
+  }
+  if (j <= max_msgs && j <= store_cmp_messages(y)) msg_off[j] = store_cmp_msg_off(y, j);
+}
+// k_cmp_encode: one aligned 32-bit word of the output per lane
+__global__ void __launch_bounds__(256) k_cmp_encode(u64 words, store_cmp_layout y, const u64 *__restrict__ msg_off, u32 n_msgs, const u64 *__restrict__ unknown,
+                                                    const u64 *__restrict__ stale, const u32 *__restrict__ flags, u8 *__restrict__ out, u64 total) {
+  const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (k < words) store_cmp_word(y, msg_off, n_msgs, unknown, stale, flags, out, total, (u32)((uintptr_t)out & 3), k);
+}
+
+extern "C" int lamd_channel_range_compare_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, size_t n, const uint8_t *msgs,
+                                                const uint64_t *moff, const uint32_t *want_first, const uint32_t *want_end, uint32_t max_unknown,
+                                                uint32_t max_stale, int8_t *status, uint32_t *per_msg, size_t scid_cap, uint64_t *unknown_scid,
+                                                uint64_t *stale_scid, uint8_t *stale_flags, size_t msg_cap, uint64_t *msg_off, uint8_t *out, void *d_out,
+                                                size_t out_cap, lamd_range_compare_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!digest || digest->ctx != ctx || !chain_hash32 || !summary || (n && (!msgs || !moff || !status || !per_msg)) || !want_first != !want_end ||
+      (scid_cap && (!unknown_scid || !stale_scid || !stale_flags)) || (msg_cap && !msg_off) || n >= (size_t)STORE_NONE ||
+      max_unknown > STORE_CMP_MAX_UNKNOWN || max_stale > STORE_CMP_MAX_STALE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_range_compare_summary();
+  store_cmp_layout y;
+  y.unknown = y.stale = 0;
+  y.max_unknown = max_unknown ? max_unknown : STORE_CMP_MAX_UNKNOWN;
+  y.max_stale = max_stale ? max_stale : STORE_CMP_MAX_STALE;
+  memcpy(y.chain, chain_hash32, 32);
+  // the framing, on the host: status, and where the entries of the accepted messages lie
+  std::vector<store_cmp_msg> pm(n);
+  std::vector<u64> first(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (moff[i + 1] < moff[i]) { ctx->err = "channel_range comparison: decreasing message offsets"; return LAMD_ERR_ARG; }
+    pm[i] = store_cmp_parse(msgs + moff[i], (size_t)(moff[i + 1] - moff[i]), moff[i], chain_hash32, want_first != nullptr, want_first ? want_first[i] : 0,
+                            want_end ? want_end[i] : 0);
+    status[i] = (int8_t)pm[i].status;
+    summary->by_status[pm[i].status < 0 ? 7 : pm[i].status]++;
+    first[i + 1] = first[i] + pm[i].n;
+    per_msg[3 * i] = per_msg[3 * i + 1] = per_msg[3 * i + 2] = 0;
+  }
+  const u64 total_entries = first[n];
+  if (total_entries >= (u64)STORE_NONE) { ctx->err = "channel_range comparison: too many entries"; return LAMD_ERR_ARG; }
+  summary->entries = total_entries;
+  if (total_entries == 0) {   // nothing to look up: no list, no message
+    if (msg_cap) msg_off[0] = 0;
+    return LAMD_OK;
+  }
+  const u32 E = (u32)total_entries;
+  const size_t n_bytes = (size_t)moff[n];
+  const u64 max_msgs = (u64)store_cmp_msgs_of(E, y.max_unknown) + store_cmp_msgs_of(E, y.max_stale);
+  lamd_ctx *L = ctx;   // queued copies read this frame's vectors: STCHK drains the stream
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  size_t tmp_bytes = 0, need = 0;
+  STCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, (size_t)E, 0, 64, st));
+  STCHK(rocprim::radix_sort_keys(nullptr, need, (const u64 *)nullptr, (u64 *)nullptr, (size_t)E, 0, 64, st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  STCHK(rocprim::inclusive_scan(nullptr, need, (const u32 *)nullptr, (u32 *)nullptr, (size_t)E, rocprim::plus<u32>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  // ent_first u64[n + 1] | unk_key, stale_key, unk_sorted, stale_sorted, unk_out, stale_out u64[E] each | msg_off u64[max_msgs + 1] | pm[n] |
+  // stale_val, stale_val_sorted, head, pos_unk, pos_stale, flags_out u32[E] each | per_msg u32[3 n] | cnt u32[CMP_CNTS] | cls u8[E] | the messages |
+  // (256-aligned) the workspace of the sorts and the scans
+  const size_t o_tmp = align_up(8 * (n + 1 + 6 * (size_t)E + max_msgs + 1) + sizeof(store_cmp_msg) * n + 4 * (6 * (size_t)E + 3 * n + CMP_CNTS) + E + n_bytes, 256);
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.cmp, o_tmp + tmp_bytes + 16)) != LAMD_OK) return rc;
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_dig.create());
+  u64 *d_first = ctx->store.cmp.as<u64>(), *d_ukey = d_first + n + 1, *d_skey = d_ukey + E, *d_usort = d_skey + E, *d_ssort = d_usort + E, *d_uout = d_ssort + E,
+      *d_sout = d_uout + E, *d_msgoff = d_sout + E;
+  store_cmp_msg *d_pm = (store_cmp_msg *)(d_msgoff + max_msgs + 1);
+  u32 *d_sval = (u32 *)(d_pm + n), *d_svsort = d_sval + E, *d_head = d_svsort + E, *d_upos = d_head + E, *d_spos = d_upos + E, *d_flags = d_spos + E,
+      *d_permsg = d_flags + E, *d_cnt = d_permsg + 3 * n;
+  u8 *d_cls = (u8 *)(d_cnt + CMP_CNTS), *d_msgs = d_cls + E;
+  void *d_tmp = ctx->store.cmp.as<u8>() + o_tmp;
+  u32 cnt[CMP_CNTS] = {};
+  std::vector<u32> h_flags;
+  STCHK(hipMemcpyAsync(d_first, first.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(d_pm, pm.data(), sizeof(store_cmp_msg) * n, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(d_msgs, msgs, n_bytes, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(d_ukey, 0xFF, 16 * (size_t)E, st));   // unk_key, stale_key
+  STCHK(hipMemsetAsync(d_sval, 0, 4 * (size_t)E, st));
+  STCHK(hipMemsetAsync(d_flags, 0, 4 * (size_t)E, st));
+  STCHK(hipMemsetAsync(d_cnt, 0, 4 * CMP_CNTS, st));
+  const dim3 grid(blocks_for(E)), block(256);
+  const store_cmp_digest dg{digest->scid, digest->ts, (u32)digest->count, digest->bare, (u32)digest->nbare};
+  if (timed) STCHK(ctx->store.t_dig.record(0, st));
+  hipLaunchKernelGGL(k_cmp_classify, grid, block, 0, st, E, (const u8 *)d_msgs, (const store_cmp_msg *)d_pm, (const u64 *)d_first, (u32)n, dg, d_cls, d_ukey, d_skey,
+                     d_sval, d_cnt);
+  hipLaunchKernelGGL(k_cmp_per_msg, dim3((unsigned)((n + 3) / 4)), block, 0, st, (u32)n, (const u64 *)d_first, (const u8 *)d_cls, d_permsg);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(1, st));
+  // stable sorts of all E slots: the pads (largest key) stay behind the real elements, whatever scids the peers sent
+  STCHK(rocprim::radix_sort_keys(d_tmp, tmp_bytes, (const u64 *)d_ukey, d_usort, (size_t)E, 0, 64, st));
+  STCHK(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (const u64 *)d_skey, d_ssort, (const u32 *)d_sval, d_svsort, (size_t)E, 0, 64, st));
+  hipLaunchKernelGGL(k_cmp_heads, grid, block, 0, st, E, (const u64 *)d_usort, (const u32 *)(d_cnt + CMP_CNT_UNKNOWN), d_head);
+  STCHK(rocprim::inclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_head, d_upos, (size_t)E, rocprim::plus<u32>(), st));
+  hipLaunchKernelGGL(k_cmp_merge, grid, block, 0, st, E, (const u64 *)d_usort, (const u32 *)nullptr, (const u32 *)(d_cnt + CMP_CNT_UNKNOWN), (const u32 *)d_upos, d_uout,
+                     (u32 *)nullptr);
+  hipLaunchKernelGGL(k_cmp_heads, grid, block, 0, st, E, (const u64 *)d_ssort, (const u32 *)(d_cnt + CMP_CNT_STALE), d_head);
+  STCHK(rocprim::inclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_head, d_spos, (size_t)E, rocprim::plus<u32>(), st));
+  hipLaunchKernelGGL(k_cmp_merge, grid, block, 0, st, E, (const u64 *)d_ssort, (const u32 *)d_svsort, (const u32 *)(d_cnt + CMP_CNT_STALE), (const u32 *)d_spos, d_sout,
+                     d_flags);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(2, st));
+  hipLaunchKernelGGL(k_cmp_plan, dim3(blocks_for((size_t)max_msgs + 1)), block, 0, st, E, (u32)max_msgs, y.max_unknown, y.max_stale, (const u32 *)d_upos,
+                     (const u32 *)d_spos, d_cnt, d_msgoff);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(3, st));
+  STCHK(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(per_msg, d_permsg, 12 * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: counts and sizes
+  if (timed) STCHK(ctx->store.t_dig.read(3, summary->stage_ms));
+  y.unknown = cnt[CMP_CNT_UNKNOWN_MERGED];
+  y.stale = cnt[CMP_CNT_STALE_MERGED];
+  const u64 n_msgs = store_cmp_messages(y), total = store_cmp_msg_off(y, n_msgs);
+  summary->entries_unknown = cnt[CMP_CNT_UNKNOWN];
+  summary->entries_stale = cnt[CMP_CNT_STALE];
+  summary->unknown = y.unknown;
+  summary->stale = y.stale;
+  summary->unknown_messages = store_cmp_msgs_of(y.unknown, y.max_unknown);
+  summary->messages = n_msgs;
+  summary->bytes = total;
+  const bool want_out = out || d_out;
+  if (y.unknown > scid_cap || y.stale > scid_cap) { ctx->err = "channel_range comparison: scid arrays too small"; return LAMD_ERR_ARG; }
+  if (n_msgs > msg_cap) { ctx->err = "channel_range comparison: msg_off too small"; return LAMD_ERR_ARG; }
+  if (want_out && total > out_cap) { ctx->err = "channel_range comparison: output buffer too small"; return LAMD_ERR_ARG; }
+  if (msg_off)
+    for (u64 j = 0; j <= n_msgs; j++) msg_off[j] = store_cmp_msg_off(y, j);   // the closed form k_cmp_plan has left on the device
+  if (n_msgs == 0) return LAMD_OK;
+  if (y.unknown) STCHK(hipMemcpyAsync(unknown_scid, d_uout, 8 * (size_t)y.unknown, hipMemcpyDeviceToHost, st));
+  if (y.stale) {
+    h_flags.resize(y.stale);
+    STCHK(hipMemcpyAsync(stale_scid, d_sout, 8 * (size_t)y.stale, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(h_flags.data(), d_flags, 4 * (size_t)y.stale, hipMemcpyDeviceToHost, st));
+  }
+  if (want_out) {
+    if (!d_out && (rc = ensure(ctx, &ctx->store.cmp_out, total + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+    u8 *d_bytes = d_out ? (u8 *)d_out : ctx->store.cmp_out.as<u8>();
+    const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+    hipLaunchKernelGGL(k_cmp_encode, dim3((unsigned)((words + 255) / 256)), block, 0, st, words, y, (const u64 *)d_msgoff, (u32)n_msgs, (const u64 *)d_uout,
+                       (const u64 *)d_sout, (const u32 *)d_flags, d_bytes, total);
+    STCHK(hipGetLastError());
+    if (timed) STCHK(ctx->store.t_dig.record(4, st));
+    if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  }
+  STCHK(hipStreamSynchronize(st));   // the second wait: the lists and the bytes
+  if (timed && want_out) {
+    float ms = 0;
+    STCHK(hipEventElapsedTime(&ms, ctx->store.t_dig.ev[3], ctx->store.t_dig.ev[4]));
+    summary->stage_ms[3] = ms;
+  }
+  for (u32 j = 0; j < y.stale; j++) stale_flags[j] = (uint8_t)h_flags[j];
+  return LAMD_OK;
+}

@@ -97,6 +97,13 @@ class StoreDigest:
         self._eng._chk(self._eng._lib.lamd_store_digest_read(self._h, n, scid.ctypes.data, ts.ctypes.data, csum.ctypes.data, rec.ctypes.data))
         return scid[:n], ts[:n], csum[:n], rec[:n]
 
+    def read_bare(self):
+        """-> scid uint64 [summary["channels_no_update"]]: the channels without an update, ascending"""
+        n = int(self._eng._lib.lamd_store_digest_bare_count(self._h)) if self._h else 0
+        scid = np.zeros(max(1, n), dtype=np.uint64)
+        self._eng._chk(self._eng._lib.lamd_store_digest_read_bare(self._h, n, scid.ctypes.data))
+        return scid[:n]
+
     def close(self):
         if self._h:
             self._eng._lib.lamd_store_digest_free(self._h)
@@ -506,6 +513,46 @@ class Engine:
         if return_summary:
             return status[:nq], replies, {k: (list(getattr(s, k)) if k == "stage_ms" else int(getattr(s, k))) for k, _ in s._fields_}
         return status[:nq], replies
+
+    def channel_range_compare(self, digest, chain_hash, msgs, want=None, max_unknown=0, max_stale=0, return_summary=False):
+        """lamd_channel_range_compare_batch: peers' raw reply_channel_range messages compared with a StoreDigest, as the seeker does.
+        chain_hash: the 32 bytes of our chain; want: optional [(range_first_blocknum, range_end_blocknum)] per message, the outstanding
+        queries; max_unknown / max_stale: scids per query_short_channel_ids message (0: 8000 / 7000).
+        -> (status int8 [msgs] (0 accepted, -1 malformed, 1..6: see the header), per_msg uint32 [msgs, 3] (entries, unknown, stale, before
+        merging), unknown uint64 (ascending, each once), stale uint64 (ascending, each once), flags uint8 (the query_flags of each stale
+        scid), [bytes, ...]: the query_short_channel_ids messages, those for the unknown list first)"""
+        chain = np.frombuffer(bytes(chain_hash), dtype=np.uint8)
+        if chain.size != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        n = len(msgs)
+        if want is not None and len(want) != n:
+            raise ValueError("one (first, end) per message")
+        moff = np.zeros(n + 1, dtype=np.uint64)
+        moff[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\x00", dtype=np.uint8)
+        wf = we = None
+        if want is not None:
+            w = np.ascontiguousarray(np.array(want, dtype=np.uint32).reshape(n, 2))
+            wf, we = np.ascontiguousarray(w[:, 0]), np.ascontiguousarray(w[:, 1])
+            wf, we = (wf if n else np.zeros(1, dtype=np.uint32)), (we if n else np.zeros(1, dtype=np.uint32))
+        status, per_msg = np.zeros(max(1, n), dtype=np.int8), np.zeros((max(1, n), 3), dtype=np.uint32)
+        s = _ffi.LamdRangeCompareSummary()
+        head = (self._ctx, digest._h, chain.ctypes.data, n, blob.ctypes.data, moff.ctypes.data, None if wf is None else wf.ctypes.data,
+                None if we is None else we.ctypes.data, int(max_unknown), int(max_stale), status.ctypes.data, per_msg.ctypes.data)
+        rc = self._lib.lamd_channel_range_compare_batch(*head, 0, None, None, None, 0, None, None, None, 0, ctypes.byref(s))          # the sizes
+        if rc < 0 and not (rc == -3 and s.messages):
+            self._chk(rc)
+        cap = max(1, s.unknown, s.stale)
+        unknown, stale, flags = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint8)
+        msg_off, out = np.zeros(s.messages + 1, dtype=np.uint64), np.zeros(max(1, s.bytes), dtype=np.uint8)
+        self._chk(self._lib.lamd_channel_range_compare_batch(*head, cap, unknown.ctypes.data, stale.ctypes.data, flags.ctypes.data, s.messages + 1,
+                                                             msg_off.ctypes.data, out.ctypes.data, None, max(1, s.bytes), ctypes.byref(s)))
+        raw = out.tobytes()
+        messages = [raw[int(msg_off[j]):int(msg_off[j + 1])] for j in range(int(s.messages))]
+        res = (status[:n], per_msg[:n], unknown[:s.unknown], stale[:s.stale], flags[:s.stale], messages)
+        if return_summary:
+            return res + ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
 
     # ---- single-item veneers (reference semantics)
     def check_signed_hash(self, hash32, sig64, pubkey):
