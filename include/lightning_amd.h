@@ -681,6 +681,93 @@ int lamd_channel_range_compare_batch(lamd_ctx *ctx, const lamd_store_digest *dig
 				     uint64_t *stale_scid, uint8_t *stale_flags, size_t msg_cap, uint64_t *msg_off, uint8_t *out, void *d_out,
 				     size_t out_cap, lamd_range_compare_summary *summary);
 
+/* ---- answering query_short_channel_ids from a store image: what handle_query_short_channel_ids() (connectd/queries.c:260-368) and
+ * maybe_create_query_responses() (:112-255) send for a peer's query, for a batch of raw queries, as copies of the stored messages.
+ *
+ * THE DIRECTORY is built from the same (image, rec_off, verdict) as a digest plus that digest; n differing from the digest's records is
+ * LAMD_ERR_ARG.  Unlike the digest it REFERS TO THE IMAGE: a host `store` is copied to the device and owned by the directory, a resident
+ * d_store is read in place and the caller keeps it alive until lamd_store_directory_free; rec_off is uploaded and kept; what it needs of
+ * the digest is copied, the digest may be freed.  Every device read stays inside the image whatever rec_off holds.  "Counts" is the
+ * digest's word: DELETED flag clear and, with verdict, verdict[i] == LAMD_STORE_OK.
+ *   CHANNEL -> RECORDS  digest entry j: its rec[3] as is.  Bare channel j: the lowest-index counting 256 of that scid (one lane per
+ *            record bisects the bare list, a 32-bit atomicMin).  The channels are numbered entries first, then the bare ones.
+ *   NODES    the distinct 33-byte node ids named by the announcements of all channels: with feature length f (the be16 at message
+ *            offset 258) node_id_1 sits at offset 300 + f and node_id_2 at 333 + f; an announcement shorter than 366 + f names no
+ *            nodes.  first = the lowest announcement record index naming the node.
+ *   RANK     the nodes ascending by memcmp of the 33 bytes; a node's rank is its position.  Node ids are attacker-chosen, so no
+ *            shortened key decides: a stable LSD sort over the 2 x channels candidates, five rocPRIM radix_sort_pairs passes over 8-byte
+ *            chunks gathered from the image (the first one the 33rd byte alone) and a one-bit pass that moves the candidates without an
+ *            id behind the others; then heads of runs, an inclusive scan, and the merge.  Each channel keeps the ranks of its two
+ *            nodes, or UINT32_MAX.
+ *   NODE ANNOUNCEMENT of a node: the HIGHEST-index counting 257 of >= 105 + f bytes (f: the be16 at offset 66, the id sits at 72 + f)
+ *            whose id is that node and whose index is greater than the node's first: the last one in the file wins whatever the
+ *            timestamps, and one in front of the node's first channel does not count (common/gossmap.c:650-668).  A 32-bit atomicMax of
+ *            index + 1; the 257 records find their node by bisection in the ranked ids.
+ * The call runs on the context's stream and waits once, at its end, for the counters. */
+typedef struct lamd_store_directory lamd_store_directory;
+typedef struct {
+	uint64_t nodes;             /* distinct node ids */
+	uint64_t nodes_announced;   /* ... of them with a node_announcement */
+	uint64_t nann_no_node, nann_in_front, nann_short;   /* counting 257 records ignored, by reason */
+	double stage_ms[5];         /* with lamd_set_timing: bare records, candidates, sort, rank, node announcements */
+} lamd_store_directory_summary;
+int lamd_gossip_store_directory_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
+				      const int8_t *verdict, const lamd_store_digest *digest, lamd_store_directory **directory,
+				      lamd_store_directory_summary *summary);
+void lamd_store_directory_free(lamd_store_directory *directory);
+size_t lamd_store_directory_node_count(const lamd_store_directory *directory);
+/* the nodes in rank order: id33[33 * cap], first[cap], nann_rec[cap] (UINT32_MAX: not announced); any may be NULL; cap < count: LAMD_ERR_ARG */
+int lamd_store_directory_read_nodes(const lamd_store_directory *directory, size_t cap, uint8_t *id33, uint32_t *first, uint32_t *nann_rec);
+/* the channels: bare_rec[cap_bare] (the announcement's record of each bare channel, in the bare list's order), entry_rank[2 * cap_entries],
+ * bare_rank[2 * cap_bare] (the ranks of node_id_1 and node_id_2, UINT32_MAX: none); any may be NULL; a cap below its count: LAMD_ERR_ARG */
+int lamd_store_directory_read_channels(const lamd_store_directory *directory, size_t cap_entries, size_t cap_bare, uint32_t *bare_rec,
+				       uint32_t *entry_rank, uint32_t *bare_rank);
+
+/* THE REPLIES.  Framing as lamd_channel_range_reply_batch: query q is queries + qoff[q] .. qoff[q + 1] (the call reads
+ * queries[qoff[0], qoff[nq])), its replies are the messages reply_first[q] .. reply_first[q + 1] - 1, message j is out + msg_off[j] ..
+ * msg_off[j + 1]; msg_rec[j] (optional) is the record index the message was copied from, UINT32_MAX for an end message.
+ * STATUS, parsed on the host (the bigsize flags are sequential), the first failure decides:
+ *   -1  not a query_short_channel_ids: shorter than 36 bytes, type not 261, len past the end, a TLV stream that breaks fromwire_tlv's rules
+ *       (ascending types, minimal bigsize, unknown even type), TLV 1 of length 0
+ *    2  TLV 1: encoding_type not 0, or a flag that is not a minimal bigsize or runs past the end (common/decode_array.c:45-82)
+ *    1  foreign chain_hash: exactly one reply, be16 262 | THEIR chain_hash | 0x00.  DELIBERATE DIFFERENCE: the call stops there; the
+ *       reference (:304-310) does not return and goes on to answer from our chain's store.
+ *    3  encoded_short_ids does not decode: len 0, first byte not 0, (len - 1) % 8 != 0 (decode_array.c:7-43)
+ *    4  the number of flags is not the number of scids
+ *    0  answered
+ *   "Bad concurrent query" (:320-323) is per-peer state, and so is the pacing of one scid per wakeup: the caller's.  This call returns
+ *   the whole answer.  A flag may be any 64-bit bigsize, bits 0..4 are looked at; without TLV 1 every flag is 0x1f.
+ * ANSWER of an accepted query, in this order:
+ *   1. for each scid OCCURRENCE, in the query's order: the channel_announcement (bit 0), the channel_update of direction 0 (bit 1, if the
+ *      slot is set), that of direction 1 (bit 2).  A duplicate scid is answered again, an unknown scid gives nothing.
+ *   2. the node_announcements of the distinct nodes asked for with bits 3 (node_id_1) and 4 (node_id_2) over the whole query, in rank
+ *      order, each once, for those that have one (uniquify_node_ids, :85-107).
+ *   3. reply_short_channel_ids_end: be16 262 | chain_hash32 | 0x01, 35 bytes.
+ *   A query with no scid (len == 1) gives the end message alone.  per_query[4 * nq]: scids, known scids, channel messages, node messages
+ *   (0, 0, 0, 0 unless answered).
+ * SIZES  msg_cap must hold the messages, out_cap the bytes (when out or d_out is given).  One too small: LAMD_ERR_ARG with summary, status,
+ *   per_query and reply_first filled in and nothing written to msg_off, msg_rec, out or d_out.  All caps 0: the sizes alone.  The bytes
+ *   go to out (host), d_out (device, any alignment), or neither.
+ * Device work, on the context's stream: k_sq_lookup (one lane per occurrence: its query by bisection in the prefix sums, the be64 scid
+ * byte by byte, two binary searches, its <= 3 records and their sizes -- the be16 len of the record header --, (query << 32 | rank) keys
+ * compacted with one atomic per wave), rocPRIM's stable radix sort of all key slots (pads of all-ones), k_cmp_heads, an inclusive scan
+ * and k_cmp_merge (each query's distinct nodes in rank order), k_sq_nodes (their announcements), two exclusive scans over occurrences
+ * and nodes (messages, bytes), k_sq_per_query and k_range_scan (every query's first message and byte), k_sq_plan (msg_off, msg_rec),
+ * k_sq_encode, one aligned 32-bit word of the output per lane, its four bytes built in registers from byte loads.  The host waits once
+ * for sizes and offsets and once for the bytes.  Limits: nq and the sum of the scids below UINT32_MAX, qoff non-decreasing, the
+ * directory built by this context. */
+typedef struct {
+	uint64_t by_status[6];   /* queries: [0] answered, [1..4] statuses 1..4, [5] malformed */
+	uint64_t scids, known;   /* occurrences in the answered queries; ... of them channels of the store */
+	uint64_t channel_messages, node_messages, end_messages;
+	uint64_t messages, bytes;   /* what msg_cap and out_cap must hold */
+	double stage_ms[4];      /* with lamd_set_timing: lookup, nodes (sort, merge, announcements), plan (scans, per query, offsets), encode */
+} lamd_scid_reply_summary;
+int lamd_short_channel_ids_reply_batch(lamd_ctx *ctx, const lamd_store_directory *directory, const uint8_t *chain_hash32, size_t nq,
+				       const uint8_t *queries, const uint64_t *qoff, int8_t *status, uint32_t *per_query, uint64_t *reply_first,
+				       size_t msg_cap, uint64_t *msg_off, uint32_t *msg_rec, uint8_t *out, void *d_out, size_t out_cap,
+				       lamd_scid_reply_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

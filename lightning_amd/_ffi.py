@@ -72,6 +72,19 @@ class LamdRangeCompareSummary(ctypes.Structure):
                 ("bytes", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 4)]
 
 
+class LamdStoreDirectorySummary(ctypes.Structure):
+    """lamd_store_directory_summary (include/lightning_amd.h): what lamd_gossip_store_directory_build reports about the directory it built"""
+    _fields_ = [("nodes", ctypes.c_uint64), ("nodes_announced", ctypes.c_uint64), ("nann_no_node", ctypes.c_uint64), ("nann_in_front", ctypes.c_uint64),
+                ("nann_short", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 5)]
+
+
+class LamdScidReplySummary(ctypes.Structure):
+    """lamd_scid_reply_summary (include/lightning_amd.h): what lamd_short_channel_ids_reply_batch reports about a batch of queries"""
+    _fields_ = [("by_status", ctypes.c_uint64 * 6), ("scids", ctypes.c_uint64), ("known", ctypes.c_uint64), ("channel_messages", ctypes.c_uint64),
+                ("node_messages", ctypes.c_uint64), ("end_messages", ctypes.c_uint64), ("messages", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("stage_ms", ctypes.c_double * 4)]
+
+
 class LamdGtableAuditResult(ctypes.Structure):
     """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
     _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
@@ -137,6 +150,14 @@ SYMBOLS = {
                                                         ctypes.POINTER(LamdRangeCompareSummary)]),
     "lamd_channel_range_reply_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
                                                       ctypes.c_void_p, c_sz, ctypes.POINTER(LamdRangeReplySummary)]),
+    "lamd_gossip_store_directory_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.c_void_p,
+                                                         ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(LamdStoreDirectorySummary)]),
+    "lamd_store_directory_free": (None, [ctypes.c_void_p]),
+    "lamd_store_directory_node_count": (c_sz, [ctypes.c_void_p]),
+    "lamd_store_directory_read_nodes": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p]),
+    "lamd_store_directory_read_channels": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_sz, c_u8p, c_u8p, c_u8p]),
+    "lamd_short_channel_ids_reply_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p,
+                                                          ctypes.c_void_p, c_sz, ctypes.POINTER(LamdScidReplySummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

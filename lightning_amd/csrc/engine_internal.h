@@ -193,10 +193,12 @@ struct lamd_ctx {
   devbuf g_msgs, g_off, g_ids, g_rowbase, g_hash, g_sig, g_pub, g_malformed, g_ok, g_verdict;
   // gossip_store calls (lamd_store.hip).  audit: image, the host walk's arrays, signers, scid index, per-record bytes; repair: reasons, sizes, offsets,
   // block sums, node table, and the output image; digest build: its tables and the sort's workspace; range replies: plan arrays, the messages;
-  // range comparison: the peers' messages, classes, lists, the sorts' workspace, and the queries it writes.
-  // t_audit / t_rep: the stage boundaries of an audit and of a repair's own stages; t_dig: those of a digest build, a range reply or a comparison
+  // range comparison: the peers' messages, classes, lists, the sorts' workspace, and the queries it writes; directory build: candidates, keys,
+  // permutations, the sorts' workspace; short_channel_ids replies: the queries, per-occurrence and per-node arrays, offsets, and the messages.
+  // t_audit / t_rep: the stage boundaries of an audit and of a repair's own stages; t_dig: those of a digest or directory build, a range reply, a
+  // comparison or a short_channel_ids reply
   struct store_ws {
-    devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out;
+    devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out, dir, sq, sq_out;
     stage_timer<6> t_audit;
     stage_timer<4> t_rep;
     stage_timer<6> t_dig;

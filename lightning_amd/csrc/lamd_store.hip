@@ -1,10 +1,12 @@
-// liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies and the comparison of peers' replies
+// liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies, the comparison of peers' replies,
+// the directory of an image and the answers to query_short_channel_ids
 #include "engine_internal.h"
 #include "store_audit.h"
 #include "store_repair.h"
 #include "store_latest.h"
 #include "store_digest.h"
 #include "store_compare.h"
+#include "store_query.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <memory>
@@ -1139,5 +1141,505 @@ extern "C" int lamd_channel_range_compare_batch(lamd_ctx *ctx, const lamd_store_
     summary->stage_ms[3] = ms;
   }
   for (u32 j = 0; j < y.stale; j++) stale_flags[j] = (uint8_t)h_flags[j];
+  return LAMD_OK;
+}
+
+// ---- the directory of a store image (lamd_gossip_store_directory_build; per-record logic in store_query.h).  cnt: DIR_CNT_* words, all 0.
+enum { DIR_CNT_VALID = 0, DIR_CNT_NODES = 1, DIR_CNT_ANNOUNCED = 2, DIR_CNT_NO_NODE = 3, DIR_CNT_IN_FRONT = 4, DIR_CNT_SHORT = 5, DIR_CNTS = 8 };
+// bare_rec: one word per bare channel, preset to all-ones bytes
+__global__ void __launch_bounds__(256) k_dir_bare(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                  const int8_t *__restrict__ verdict, const u64 *__restrict__ bare, u32 nbare, u32 *bare_rec) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_dir_bare_one(store, store_len, rec_off, verdict, i, bare, nbare, bare_rec);
+}
+// one lane per channel c (the entries, then the bare ones): candidates 2 c and 2 c + 1 are its two node ids, or name none
+__global__ void __launch_bounds__(256) k_dir_cand(u32 channels, u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                  const u32 *__restrict__ ent_rec, u32 count, const u32 *__restrict__ bare_rec, u64 *__restrict__ cand_off,
+                                                  u32 *__restrict__ cand_rec, u32 *__restrict__ perm, u32 *cnt) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  bool ok = false;
+  if (c < channels) {
+    const u32 a = c < count ? ent_rec[3 * (size_t)c] : bare_rec[c - count];
+    u64 idoff = 0;
+    ok = a < n && store_dir_cann_ids(store, store_len, rec_off[a], &idoff);
+    for (u32 k = 0; k < 2; k++) {
+      cand_off[2 * (size_t)c + k] = ok ? idoff + 33 * k : STORE_DIR_NO_ID;
+      cand_rec[2 * (size_t)c + k] = a;
+      perm[2 * (size_t)c + k] = 2 * c + k;
+    }
+  }
+  const u64 mask = __ballot(ok);
+  if ((threadIdx.x & 63u) == 0 && mask) atomicAdd(&cnt[DIR_CNT_VALID], 2 * (u32)__popcll(mask));
+}
+__global__ void __launch_bounds__(256) k_dir_keys(u32 m, const u8 *__restrict__ store, const u64 *__restrict__ cand_off, const u32 *__restrict__ perm, u32 pass,
+                                                  u64 *__restrict__ key) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j < m) key[j] = store_dir_pass_key(store, cand_off[perm[j]], pass);
+}
+__global__ void __launch_bounds__(256) k_dir_heads(u32 m, const u8 *__restrict__ store, const u64 *__restrict__ cand_off, const u32 *__restrict__ perm,
+                                                   const u32 *__restrict__ cnt, u32 *__restrict__ head) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= m) return;
+  head[j] = store_dir_head(store, cand_off, perm, cnt[DIR_CNT_VALID] < m ? cnt[DIR_CNT_VALID] : m, j);
+}
+// chan_rank: preset to all-ones bytes, node_first too; the lane of the last candidate with an id leaves the number of nodes
+__global__ void __launch_bounds__(256) k_dir_merge(u32 m, const u64 *__restrict__ cand_off, const u32 *__restrict__ cand_rec, const u32 *__restrict__ perm,
+                                                   const u32 *__restrict__ head, const u32 *__restrict__ pos, u32 *__restrict__ chan_rank,
+                                                   u64 *__restrict__ node_off, u32 *node_first, u32 *cnt) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  const u32 valid = cnt[DIR_CNT_VALID] < m ? cnt[DIR_CNT_VALID] : m;
+  if (j >= valid) return;
+  const u32 r = pos[j] - 1, c = perm[j];
+  chan_rank[c] = r;
+  if (head[j]) node_off[r] = cand_off[c];
+  atomicMin(&node_first[r], cand_rec[c]);
+  if (j == valid - 1) cnt[DIR_CNT_NODES] = pos[j];
+}
+// node_nann: one word per node, preset to 0
+__global__ void __launch_bounds__(256) k_dir_nann(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                  const int8_t *__restrict__ verdict, const u64 *__restrict__ node_off, const u32 *__restrict__ node_first,
+                                                  u32 *node_nann, u32 *cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  const u32 r = i < n ? store_dir_nann_one(store, store_len, rec_off, verdict, i, node_off, node_first, cnt[DIR_CNT_NODES], node_nann) : (u32)STORE_DIR_NANN_NONE;
+  wave_count(&cnt[DIR_CNT_NO_NODE], r == STORE_DIR_NANN_NO_NODE);
+  wave_count(&cnt[DIR_CNT_IN_FRONT], r == STORE_DIR_NANN_IN_FRONT);
+  wave_count(&cnt[DIR_CNT_SHORT], r == STORE_DIR_NANN_SHORT);
+}
+__global__ void __launch_bounds__(256) k_dir_announced(u32 m, const u32 *__restrict__ node_nann, u32 *cnt) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  wave_count(&cnt[DIR_CNT_ANNOUNCED], j < m && j < cnt[DIR_CNT_NODES] && node_nann[j] != 0);
+}
+// the nodes' ids, gathered for lamd_store_directory_read_nodes: one lane per byte
+__global__ void __launch_bounds__(256) k_dir_ids(u32 nodes, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ node_off, u8 *__restrict__ ids) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= 33 * (size_t)nodes) return;
+  const u64 at = node_off[j / 33] + j % 33;
+  ids[j] = at < store_len ? store[at] : 0;
+}
+
+struct lamd_store_directory {
+  lamd_ctx *ctx = nullptr;
+  void *mem = nullptr;          // rec_off u64[n] | scid u64[channels] | node_off u64[2 channels] | ent_rec u32[3 count] | bare_rec u32[nbare] |
+                                // chan_rank, node_first, node_nann u32[2 channels] each | the image, unless it is the caller's
+  const u8 *img = nullptr;      // the image on the device: inside mem, or the caller's d_store
+  size_t img_len = 0, n = 0, count = 0, nbare = 0, nodes = 0;
+  u64 *rec_off = nullptr, *scid = nullptr, *node_off = nullptr;   // scid: the entries' scids, then the bare ones
+  u32 *ent_rec = nullptr, *bare_rec = nullptr, *chan_rank = nullptr, *node_first = nullptr, *node_nann = nullptr;
+  store_sq_dir view() const {
+    return store_sq_dir{img, img_len, rec_off, (u32)n, scid, ent_rec, (u32)count, scid + count, bare_rec, (u32)nbare, chan_rank, node_nann, (u32)nodes};
+  }
+};
+extern "C" void lamd_store_directory_free(lamd_store_directory *d) {
+  if (!d) return;
+  if (d->mem) {
+    (void)hipSetDevice(d->ctx->device);
+    (void)hipFree(d->mem);
+  }
+  delete d;
+}
+extern "C" size_t lamd_store_directory_node_count(const lamd_store_directory *d) { return d ? d->nodes : 0; }
+extern "C" int lamd_store_directory_read_nodes(const lamd_store_directory *d, size_t cap, uint8_t *id33, uint32_t *first, uint32_t *nann_rec) {
+  if (!d) return LAMD_ERR_ARG;
+  lamd_ctx *ctx = d->ctx;
+  if (cap < d->nodes) { ctx->err = "gossip_store directory: arrays too small"; return LAMD_ERR_ARG; }
+  if (d->nodes == 0) return LAMD_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (id33) {
+    void *ids = nullptr;
+    HIPCHK(ctx, hipMalloc(&ids, 33 * d->nodes));
+    hipLaunchKernelGGL(k_dir_ids, dim3(blocks_for(33 * d->nodes)), dim3(256), 0, ctx->stream, (u32)d->nodes, d->img, d->img_len, (const u64 *)d->node_off, (u8 *)ids);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(id33, ids, 33 * d->nodes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    else (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(ids);
+    HIPCHK(ctx, e);
+  }
+  if (first) HIPCHK(ctx, hipMemcpy(first, d->node_first, 4 * d->nodes, hipMemcpyDeviceToHost));
+  if (nann_rec) {
+    HIPCHK(ctx, hipMemcpy(nann_rec, d->node_nann, 4 * d->nodes, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < d->nodes; r++) nann_rec[r] -= 1;   // index + 1, 0: none -> index, UINT32_MAX: none
+  }
+  return LAMD_OK;
+}
+extern "C" int lamd_store_directory_read_channels(const lamd_store_directory *d, size_t cap_entries, size_t cap_bare, uint32_t *bare_rec, uint32_t *entry_rank,
+                                                  uint32_t *bare_rank) {
+  if (!d) return LAMD_ERR_ARG;
+  lamd_ctx *ctx = d->ctx;
+  if (cap_entries < d->count || cap_bare < d->nbare) { ctx->err = "gossip_store directory: arrays too small"; return LAMD_ERR_ARG; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (bare_rec && d->nbare) HIPCHK(ctx, hipMemcpy(bare_rec, d->bare_rec, 4 * d->nbare, hipMemcpyDeviceToHost));
+  if (entry_rank && d->count) HIPCHK(ctx, hipMemcpy(entry_rank, d->chan_rank, 8 * d->count, hipMemcpyDeviceToHost));
+  if (bare_rank && d->nbare) HIPCHK(ctx, hipMemcpy(bare_rank, d->chan_rank + 2 * d->count, 8 * d->nbare, hipMemcpyDeviceToHost));
+  return LAMD_OK;
+}
+extern "C" int lamd_gossip_store_directory_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
+                                                 const int8_t *verdict, const lamd_store_digest *digest, lamd_store_directory **directory,
+                                                 lamd_store_directory_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (directory) *directory = nullptr;
+  if ((!store && !d_store) || !digest || digest->ctx != ctx || !directory || !summary || (n && !rec_off) || n != digest->cap) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_store_directory_summary();
+  std::unique_ptr<lamd_store_directory, void (*)(lamd_store_directory *)> D(new (std::nothrow) lamd_store_directory(), lamd_store_directory_free);
+  if (!D) return LAMD_ERR_NOMEM;
+  D->ctx = ctx;
+  D->n = n;
+  D->count = digest->count;
+  D->nbare = digest->nbare;
+  D->img_len = len;
+  if (n == 0) { *directory = D.release(); return LAMD_OK; }
+  const size_t count = D->count, nbare = D->nbare, channels = count + nbare, m = 2 * channels;   // channels <= n < 2^31
+  lamd_ctx *L = ctx;   // queued copies read the caller's arrays: an error return drains the stream (drain_fail), then the directory frees itself
+  hipStream_t st = ctx->stream;
+  const size_t o_img = 8 * (n + channels + m) + 4 * (3 * count + nbare + 3 * m);
+  hipError_t e0 = hipSetDevice(ctx->device);
+  if (e0 == hipSuccess) e0 = hipMalloc(&D->mem, o_img + (d_store ? 0 : len) + 16);
+  if (e0 != hipSuccess) {
+    ctx->err = std::string("gossip_store directory: ") + hipGetErrorString(e0);
+    return drain_fail(ctx, L, e0 == hipErrorOutOfMemory ? LAMD_ERR_NOMEM : LAMD_ERR_HIP);
+  }
+  D->rec_off = (u64 *)D->mem;
+  D->scid = D->rec_off + n;
+  D->node_off = D->scid + channels;
+  D->ent_rec = (u32 *)(D->node_off + m);
+  D->bare_rec = D->ent_rec + 3 * count;
+  D->chan_rank = D->bare_rec + nbare;
+  D->node_first = D->chan_rank + m;
+  D->node_nann = D->node_first + m;
+  D->img = d_store ? (const u8 *)d_store : (const u8 *)D->mem + o_img;
+  size_t tmp_bytes = 0, need = 0;
+  if (m) {
+    STCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, m, 0, 64, st));
+    STCHK(rocprim::inclusive_scan(nullptr, need, (const u32 *)nullptr, (u32 *)nullptr, m, rocprim::plus<u32>(), st));
+    if (need > tmp_bytes) tmp_bytes = need;
+  }
+  // cand_off, key_in, key_out u64[m] each | cand_rec, perm_a, perm_b, head, pos u32[m] each | cnt u32[DIR_CNTS] | verdict i8[n] | (256-aligned) the sorts' workspace
+  const size_t o_tmp = align_up(24 * m + 20 * m + 4 * DIR_CNTS + n, 256);
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.dir, o_tmp + tmp_bytes + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_dig.create());
+  u64 *d_coff = ctx->store.dir.as<u64>(), *d_kin = d_coff + m, *d_kout = d_kin + m;
+  u32 *d_crec = (u32 *)(d_kout + m), *d_perm = d_crec + m, *d_perm2 = d_perm + m, *d_head = d_perm2 + m, *d_pos = d_head + m, *d_cnt = d_pos + m;
+  int8_t *d_verdict = verdict ? (int8_t *)(d_cnt + DIR_CNTS) : nullptr;
+  void *d_tmp = ctx->store.dir.as<u8>() + o_tmp;
+  const u8 *img = D->img;
+  if (!d_store) STCHK(hipMemcpyAsync((void *)img, store, len, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(D->rec_off, rec_off, 8 * n, hipMemcpyHostToDevice, st));
+  if (verdict) STCHK(hipMemcpyAsync(d_verdict, verdict, n, hipMemcpyHostToDevice, st));
+  if (count) {
+    STCHK(hipMemcpyAsync(D->scid, digest->scid, 8 * count, hipMemcpyDeviceToDevice, st));
+    STCHK(hipMemcpyAsync(D->ent_rec, digest->rec, 12 * count, hipMemcpyDeviceToDevice, st));
+  }
+  if (nbare) STCHK(hipMemcpyAsync(D->scid + count, digest->bare, 8 * nbare, hipMemcpyDeviceToDevice, st));
+  if (m) {
+    STCHK(hipMemsetAsync(D->bare_rec, 0xFF, 4 * (nbare + 2 * m), st));   // bare_rec, chan_rank, node_first
+    STCHK(hipMemsetAsync(D->node_nann, 0, 4 * m, st));
+  }
+  STCHK(hipMemsetAsync(d_cnt, 0, 4 * DIR_CNTS, st));
+  const dim3 grid(blocks_for(n)), gm(blocks_for(m)), block(256);
+  if (timed) STCHK(ctx->store.t_dig.record(0, st));
+  if (nbare)
+    hipLaunchKernelGGL(k_dir_bare, grid, block, 0, st, (u32)n, img, len, (const u64 *)D->rec_off, (const int8_t *)d_verdict, (const u64 *)(D->scid + count), (u32)nbare,
+                       D->bare_rec);
+  if (timed) STCHK(ctx->store.t_dig.record(1, st));
+  if (m) {
+    hipLaunchKernelGGL(k_dir_cand, dim3(blocks_for(channels)), block, 0, st, (u32)channels, (u32)n, img, len, (const u64 *)D->rec_off, (const u32 *)D->ent_rec, (u32)count,
+                       (const u32 *)D->bare_rec, d_coff, d_crec, d_perm, d_cnt);
+    STCHK(hipGetLastError());
+  }
+  if (timed) STCHK(ctx->store.t_dig.record(2, st));
+  if (m) {
+    // stable, least significant chunk first; the one-bit pass last: the candidates without an id end behind all others, whatever ids there are
+    for (u32 pass = 0; pass < STORE_DIR_PASSES; pass++) {
+      hipLaunchKernelGGL(k_dir_keys, gm, block, 0, st, (u32)m, img, (const u64 *)d_coff, (const u32 *)d_perm, pass, d_kin);
+      STCHK(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (const u64 *)d_kin, d_kout, (const u32 *)d_perm, d_perm2, m, 0, pass == 0 ? 8 : pass == 5 ? 1 : 64, st));
+      std::swap(d_perm, d_perm2);
+    }
+  }
+  if (timed) STCHK(ctx->store.t_dig.record(3, st));
+  if (m) {
+    hipLaunchKernelGGL(k_dir_heads, gm, block, 0, st, (u32)m, img, (const u64 *)d_coff, (const u32 *)d_perm, (const u32 *)d_cnt, d_head);
+    STCHK(rocprim::inclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_head, d_pos, m, rocprim::plus<u32>(), st));
+    hipLaunchKernelGGL(k_dir_merge, gm, block, 0, st, (u32)m, (const u64 *)d_coff, (const u32 *)d_crec, (const u32 *)d_perm, (const u32 *)d_head, (const u32 *)d_pos,
+                       D->chan_rank, D->node_off, D->node_first, d_cnt);
+    STCHK(hipGetLastError());
+  }
+  if (timed) STCHK(ctx->store.t_dig.record(4, st));
+  if (m) {
+    hipLaunchKernelGGL(k_dir_nann, grid, block, 0, st, (u32)n, img, len, (const u64 *)D->rec_off, (const int8_t *)d_verdict, (const u64 *)D->node_off,
+                       (const u32 *)D->node_first, D->node_nann, d_cnt);
+    hipLaunchKernelGGL(k_dir_announced, gm, block, 0, st, (u32)m, (const u32 *)D->node_nann, d_cnt);
+    STCHK(hipGetLastError());
+  }
+  if (timed) STCHK(ctx->store.t_dig.record(5, st));
+  u32 cnt[DIR_CNTS] = {};
+  STCHK(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed) STCHK(ctx->store.t_dig.read(5, summary->stage_ms));
+  D->nodes = cnt[DIR_CNT_NODES];
+  summary->nodes = cnt[DIR_CNT_NODES];
+  summary->nodes_announced = cnt[DIR_CNT_ANNOUNCED];
+  summary->nann_no_node = cnt[DIR_CNT_NO_NODE];
+  summary->nann_in_front = cnt[DIR_CNT_IN_FRONT];
+  summary->nann_short = cnt[DIR_CNT_SHORT];
+  *directory = D.release();
+  return LAMD_OK;
+}
+
+// ---- query_short_channel_ids answers (lamd_short_channel_ids_reply_batch; per-occurrence and per-word logic in store_query.h).  The items of a
+// batch with S occurrences: item e < S is occurrence e, item S + j is slot j of the sorted distinct (query, rank) keys (2 S slots), item 3 S closes
+// the scans.  cnt: SQ_CNT_* words, all 0.
+enum { SQ_CNT_KEYS = 0, SQ_CNT_NODES = 1, SQ_CNTS = 4 };
+// k_sq_lookup: one lane per occurrence; occ_first[nq + 1]: the prefix sums of the answered queries' scid counts; scid_at[q]: where query q's scids
+// start in `bytes`; nkey: 2 S keys preset to all-ones bytes, the real ones compacted in any order
+__global__ void __launch_bounds__(256) k_sq_lookup(u32 S, const u8 *__restrict__ bytes, const u64 *__restrict__ scid_at, const u64 *__restrict__ occ_first, u32 nq,
+                                                   const u8 *__restrict__ flags, store_sq_dir d, u32 *__restrict__ occ_rec, u32 *__restrict__ icnt,
+                                                   u32 *__restrict__ ibytes, u8 *__restrict__ known, u64 *__restrict__ nkey, u32 *cnt) {
+  const u32 e = blockIdx.x * 256 + threadIdx.x;
+  u32 rank2[2] = {STORE_NONE, STORE_NONE}, q = 0;
+  if (e < S) {
+    q = store_range_locate(occ_first, nq, e);
+    u32 rec3[3], b;
+    known[e] = store_sq_lookup(d, store_be64(bytes + scid_at[q] + 8 * (u64)(e - occ_first[q])), flags[e], rec3, &b, rank2);
+    for (u32 k = 0; k < 3; k++) occ_rec[3 * (size_t)e + k] = rec3[k];
+    icnt[e] = (rec3[0] != STORE_NONE) + (rec3[1] != STORE_NONE) + (rec3[2] != STORE_NONE);
+    ibytes[e] = b;
+  }
+  for (u32 k = 0; k < 2; k++) {
+    const bool pred = rank2[k] != STORE_NONE;
+    const u32 p = wave_alloc(&cnt[SQ_CNT_KEYS], pred, 0, nullptr);
+    if (pred && p < 2 * S) nkey[p] = ((u64)q << 32) | rank2[k];
+  }
+}
+// k_sq_nodes: one lane per slot of the distinct keys (uniq; npos: the scan that numbered them) and one for the closing item: the node's announcement
+__global__ void __launch_bounds__(256) k_sq_nodes(u32 S, const u64 *__restrict__ uniq, const u32 *__restrict__ npos, u32 *cnt, store_sq_dir d,
+                                                  u32 *__restrict__ node_rec, u32 *__restrict__ icnt, u32 *__restrict__ ibytes) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j > 2 * S) return;
+  const u32 ck = cnt[SQ_CNT_KEYS] < 2 * S ? cnt[SQ_CNT_KEYS] : 2 * S, U = ck ? npos[ck - 1] : 0;
+  if (j == 0) cnt[SQ_CNT_NODES] = U;
+  u32 rec = STORE_NONE, len = 0;
+  if (j < U) {
+    const u32 rank = (u32)uniq[j], nn = rank < d.nodes ? d.node_nann[rank] : 0;
+    len = nn ? store_sq_msg_len(d, nn - 1) : 0;
+    if (len) rec = nn - 1;
+  }
+  if (j < 2 * S) node_rec[j] = rec;
+  icnt[S + j] = rec != STORE_NONE;
+  ibytes[S + j] = len;
+}
+// k_sq_per_query: one WAVE per query sums its known occurrences; lane 0 reads the rest off the scans: per_query[4 q ..] = scids, known, channel
+// messages, node messages; n_msgs / n_bytes: all its replies; qlo[q]: its first slot among the distinct keys
+__global__ void __launch_bounds__(256) k_sq_per_query(u32 nq, u32 S, const int8_t *__restrict__ status, const u64 *__restrict__ occ_first,
+                                                      const u8 *__restrict__ known, const u64 *__restrict__ uniq, const u32 *__restrict__ cnt,
+                                                      const u64 *__restrict__ mscan, const u64 *__restrict__ bscan, u32 *__restrict__ per_query,
+                                                      u32 *__restrict__ n_msgs, u64 *__restrict__ n_bytes, u32 *__restrict__ qlo) {
+  const u32 q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (q >= nq) return;   // (the whole wave)
+  const u64 a = occ_first[q], b = occ_first[q + 1];
+  u32 kn = 0;
+  for (u64 e = a + lane; e < b; e += 64) kn += known[e];
+  for (int o = 32; o; o >>= 1) kn += __shfl_down(kn, o);
+  if (lane) return;
+  u32 pq[4] = {0, 0, 0, 0}, msgs = 0, lo = 0;
+  u64 bytes = 0;
+  if (status[q] == STORE_SQ_ANSWERED) {
+    const u32 U = cnt[SQ_CNT_NODES], hi = store_sq_lower(uniq, U, ((u64)q + 1) << 32);
+    lo = store_sq_lower(uniq, U, (u64)q << 32);
+    pq[0] = (u32)(b - a);
+    pq[1] = kn;
+    pq[2] = (u32)(mscan[b] - mscan[a]);
+    pq[3] = (u32)(mscan[S + hi] - mscan[S + lo]);
+    msgs = pq[2] + pq[3] + 1;
+    bytes = (bscan[b] - bscan[a]) + (bscan[S + hi] - bscan[S + lo]) + STORE_SQ_END_BYTES;
+  } else if (status[q] == STORE_SQ_FOREIGN) {
+    msgs = 1;
+    bytes = STORE_SQ_END_BYTES;
+  }
+  for (u32 k = 0; k < 4; k++) per_query[4 * (size_t)q + k] = pq[k];
+  n_msgs[q] = msgs;
+  n_bytes[q] = bytes;
+  qlo[q] = lo;
+}
+// k_sq_plan: one lane per item and per query: where each message starts and which record it copies (STORE_NONE: an end message)
+__global__ void __launch_bounds__(256) k_sq_plan(u32 S, u32 nq, const int8_t *__restrict__ status, const u64 *__restrict__ occ_first,
+                                                 const u32 *__restrict__ occ_rec, const u32 *__restrict__ node_rec, const u64 *__restrict__ uniq,
+                                                 const u32 *__restrict__ cnt, const u32 *__restrict__ qlo, const u64 *__restrict__ mscan,
+                                                 const u64 *__restrict__ bscan, const u64 *__restrict__ msg_first, const u64 *__restrict__ byte_first,
+                                                 store_sq_dir d, u64 *__restrict__ msg_off, u32 *__restrict__ msg_rec) {
+  const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (i < S) {
+    const u32 q = store_range_locate(occ_first, nq, i);
+    const u64 a = occ_first[q];
+    u64 mi = msg_first[q] + (mscan[i] - mscan[a]), bo = byte_first[q] + (bscan[i] - bscan[a]);
+    for (u32 k = 0; k < 3; k++) {
+      const u32 r = occ_rec[3 * i + k];
+      if (r == STORE_NONE) continue;
+      msg_off[mi] = bo;
+      msg_rec[mi++] = r;
+      bo += store_sq_msg_len(d, r);
+    }
+  } else if (i < 3 * (u64)S) {
+    const u64 j = i - S;
+    if (j >= cnt[SQ_CNT_NODES] || node_rec[j] == STORE_NONE) return;
+    const u32 q = (u32)(uniq[j] >> 32);
+    const u64 a = occ_first[q], b = occ_first[q + 1], lo = qlo[q];
+    const u64 mi = msg_first[q] + (mscan[b] - mscan[a]) + (mscan[S + j] - mscan[S + lo]);
+    msg_off[mi] = byte_first[q] + (bscan[b] - bscan[a]) + (bscan[S + j] - bscan[S + lo]);
+    msg_rec[mi] = node_rec[j];
+  } else if (i < 3 * (u64)S + nq) {
+    const u32 q = (u32)(i - 3 * (u64)S);
+    if (status[q] == STORE_SQ_ANSWERED || status[q] == STORE_SQ_FOREIGN) {
+      msg_off[msg_first[q + 1] - 1] = byte_first[q + 1] - STORE_SQ_END_BYTES;
+      msg_rec[msg_first[q + 1] - 1] = STORE_NONE;
+    }
+    if (q == nq - 1) msg_off[msg_first[nq]] = byte_first[nq];
+  }
+}
+// k_sq_encode: one aligned 32-bit word of the output per lane
+__global__ void __launch_bounds__(256) k_sq_encode(u64 words, store_sq_dir d, store_sq_out o, u8 *__restrict__ out, u64 total) {
+  const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (k < words) store_sq_word(d, o, out, total, (u32)((uintptr_t)out & 3), k);
+}
+
+extern "C" int lamd_short_channel_ids_reply_batch(lamd_ctx *ctx, const lamd_store_directory *directory, const uint8_t *chain_hash32, size_t nq,
+                                                  const uint8_t *queries, const uint64_t *qoff, int8_t *status, uint32_t *per_query, uint64_t *reply_first,
+                                                  size_t msg_cap, uint64_t *msg_off, uint32_t *msg_rec, uint8_t *out, void *d_out, size_t out_cap,
+                                                  lamd_scid_reply_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!directory || directory->ctx != ctx || !chain_hash32 || !summary || !reply_first || (nq && (!queries || !qoff || !status || !per_query)) ||
+      (msg_cap && !msg_off) || nq >= (size_t)STORE_NONE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_scid_reply_summary();
+  reply_first[0] = 0;
+  if (nq == 0) {
+    if (msg_cap) msg_off[0] = 0;
+    return LAMD_OK;
+  }
+  // the framing, on the host: status, where the scids of the answered queries lie, and their flags, one byte each
+  const u64 q0 = qoff[0];
+  std::vector<u64> first(nq + 1, 0), q_at(nq), scid_at(nq, 0);
+  std::vector<store_sq_query> pq(nq);
+  for (size_t q = 0; q < nq; q++) {
+    if (qoff[q + 1] < qoff[q]) { ctx->err = "short_channel_ids replies: decreasing query offsets"; return LAMD_ERR_ARG; }
+    pq[q] = store_sq_parse(queries + qoff[q], (size_t)(qoff[q + 1] - qoff[q]), qoff[q] - q0, chain_hash32);
+    status[q] = (int8_t)pq[q].status;
+    summary->by_status[pq[q].status < 0 ? 5 : pq[q].status]++;
+    summary->end_messages += pq[q].status == STORE_SQ_ANSWERED || pq[q].status == STORE_SQ_FOREIGN;
+    first[q + 1] = first[q] + pq[q].n;
+    q_at[q] = qoff[q] - q0;
+    scid_at[q] = pq[q].scid_at;
+  }
+  if (first[nq] >= (u64)STORE_NONE) { ctx->err = "short_channel_ids replies: too many scids"; return LAMD_ERR_ARG; }
+  const size_t S = (size_t)first[nq], K = 2 * S, I1 = 3 * S + 1, MM = 5 * S + nq + 1, n_bytes = (size_t)(qoff[nq] - q0);
+  summary->scids = S;
+  std::vector<u8> flags(S + 1);
+  for (size_t q = 0; q < nq; q++)
+    if (pq[q].n) store_sq_flags(queries + qoff[q], pq[q], flags.data() + first[q]);
+  lamd_ctx *L = ctx;   // queued copies read this frame's vectors: STCHK drains the stream
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  size_t tmp_bytes = 0, need = 0;
+  if (S) {
+    STCHK(rocprim::radix_sort_keys(nullptr, tmp_bytes, (const u64 *)nullptr, (u64 *)nullptr, K, 0, 64, st));
+    STCHK(rocprim::inclusive_scan(nullptr, need, (const u32 *)nullptr, (u32 *)nullptr, K, rocprim::plus<u32>(), st));
+    if (need > tmp_bytes) tmp_bytes = need;
+  }
+  STCHK(rocprim::exclusive_scan(nullptr, need, (const u32 *)nullptr, (u64 *)nullptr, (u64)0, I1, rocprim::plus<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  // occ_first u64[nq + 1] | q_at, scid_at u64[nq] each | nkey, nsort, uniq u64[K] each | mscan, bscan u64[I1] each | msg_first, byte_first u64[nq + 1] each |
+  // n_bytes u64[nq] | msg_off u64[MM] | occ_rec u32[3 S] | node_rec, head, npos u32[K] each | icnt, ibytes u32[I1] each | n_msgs, qlo u32[nq] each |
+  // per_query u32[4 nq] | msg_rec u32[MM] | cnt u32[SQ_CNTS] | known, flags u8[S] each | status i8[nq] | the queries | (256-aligned) the sort's and the scans' workspace
+  const size_t o_tmp = align_up(8 * (6 * nq + 3 + 3 * K + 2 * I1 + MM) + 4 * (3 * S + 3 * K + 2 * I1 + 6 * nq + MM + SQ_CNTS) + 2 * S + nq + n_bytes, 256);
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.sq, o_tmp + tmp_bytes + 16)) != LAMD_OK) return rc;
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_dig.create());
+  u64 *d_first = ctx->store.sq.as<u64>(), *d_qat = d_first + nq + 1, *d_scidat = d_qat + nq, *d_nkey = d_scidat + nq, *d_nsort = d_nkey + K, *d_uniq = d_nsort + K,
+      *d_mscan = d_uniq + K, *d_bscan = d_mscan + I1, *d_mfirst = d_bscan + I1, *d_bfirst = d_mfirst + nq + 1, *d_nbytes = d_bfirst + nq + 1, *d_msgoff = d_nbytes + nq;
+  u32 *d_occrec = (u32 *)(d_msgoff + MM), *d_noderec = d_occrec + 3 * S, *d_head = d_noderec + K, *d_npos = d_head + K, *d_icnt = d_npos + K, *d_ibytes = d_icnt + I1,
+      *d_nmsgs = d_ibytes + I1, *d_qlo = d_nmsgs + nq, *d_perq = d_qlo + nq, *d_msgrec = d_perq + 4 * nq, *d_cnt = d_msgrec + MM;
+  u8 *d_known = (u8 *)(d_cnt + SQ_CNTS), *d_flags = d_known + S, *d_queries = d_flags + S + nq;
+  int8_t *d_status = (int8_t *)(d_flags + S);
+  void *d_tmp = ctx->store.sq.as<u8>() + o_tmp;
+  std::vector<u64> h_first(2 * (nq + 1));
+  STCHK(hipMemcpyAsync(d_first, first.data(), 8 * (nq + 1), hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(d_qat, q_at.data(), 8 * nq, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(d_scidat, scid_at.data(), 8 * nq, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(d_status, status, nq, hipMemcpyHostToDevice, st));
+  if (n_bytes) STCHK(hipMemcpyAsync(d_queries, queries + q0, n_bytes, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(d_cnt, 0, 4 * SQ_CNTS, st));
+  const store_sq_dir dv = directory->view();
+  const dim3 block(256);
+  if (timed) STCHK(ctx->store.t_dig.record(0, st));
+  if (S) {
+    STCHK(hipMemcpyAsync(d_flags, flags.data(), S, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(d_nkey, 0xFF, 8 * K, st));
+    hipLaunchKernelGGL(k_sq_lookup, dim3(blocks_for(S)), block, 0, st, (u32)S, (const u8 *)d_queries, (const u64 *)d_scidat, (const u64 *)d_first, (u32)nq,
+                       (const u8 *)d_flags, dv, d_occrec, d_icnt, d_ibytes, d_known, d_nkey, d_cnt);
+    STCHK(hipGetLastError());
+  }
+  if (timed) STCHK(ctx->store.t_dig.record(1, st));
+  if (S) {
+    // a stable sort of all 2 S slots: the pads (largest key) stay behind the real keys
+    STCHK(rocprim::radix_sort_keys(d_tmp, tmp_bytes, (const u64 *)d_nkey, d_nsort, K, 0, 64, st));
+    hipLaunchKernelGGL(k_cmp_heads, dim3(blocks_for(K)), block, 0, st, (u32)K, (const u64 *)d_nsort, (const u32 *)(d_cnt + SQ_CNT_KEYS), d_head);
+    STCHK(rocprim::inclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_head, d_npos, K, rocprim::plus<u32>(), st));
+    hipLaunchKernelGGL(k_cmp_merge, dim3(blocks_for(K)), block, 0, st, (u32)K, (const u64 *)d_nsort, (const u32 *)nullptr, (const u32 *)(d_cnt + SQ_CNT_KEYS),
+                       (const u32 *)d_npos, d_uniq, (u32 *)nullptr);
+  }
+  hipLaunchKernelGGL(k_sq_nodes, dim3(blocks_for(K + 1)), block, 0, st, (u32)S, (const u64 *)d_uniq, (const u32 *)d_npos, d_cnt, dv, d_noderec, d_icnt, d_ibytes);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(2, st));
+  STCHK(rocprim::exclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_icnt, d_mscan, (u64)0, I1, rocprim::plus<u64>(), st));
+  STCHK(rocprim::exclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_ibytes, d_bscan, (u64)0, I1, rocprim::plus<u64>(), st));
+  hipLaunchKernelGGL(k_sq_per_query, dim3((unsigned)((nq + 3) / 4)), block, 0, st, (u32)nq, (u32)S, (const int8_t *)d_status, (const u64 *)d_first, (const u8 *)d_known,
+                     (const u64 *)d_uniq, (const u32 *)d_cnt, (const u64 *)d_mscan, (const u64 *)d_bscan, d_perq, d_nmsgs, d_nbytes, d_qlo);
+  hipLaunchKernelGGL(k_range_scan, dim3(1), block, 0, st, (u32)nq, (const u32 *)d_nmsgs, (const u64 *)d_nbytes, d_mfirst, d_bfirst);
+  hipLaunchKernelGGL(k_sq_plan, dim3(blocks_for(3 * S + nq)), block, 0, st, (u32)S, (u32)nq, (const int8_t *)d_status, (const u64 *)d_first, (const u32 *)d_occrec,
+                     (const u32 *)d_noderec, (const u64 *)d_uniq, (const u32 *)d_cnt, (const u32 *)d_qlo, (const u64 *)d_mscan, (const u64 *)d_bscan,
+                     (const u64 *)d_mfirst, (const u64 *)d_bfirst, dv, d_msgoff, d_msgrec);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(3, st));
+  STCHK(hipMemcpyAsync(h_first.data(), d_mfirst, 16 * (nq + 1), hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(per_query, d_perq, 16 * nq, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: sizes and offsets
+  if (timed) STCHK(ctx->store.t_dig.read(3, summary->stage_ms));
+  const u64 n_msgs = h_first[nq], total = h_first[2 * nq + 1];
+  memcpy(reply_first, h_first.data(), 8 * (nq + 1));
+  for (size_t q = 0; q < nq; q++) {
+    summary->known += per_query[4 * q + 1];
+    summary->channel_messages += per_query[4 * q + 2];
+    summary->node_messages += per_query[4 * q + 3];
+  }
+  summary->messages = n_msgs;
+  summary->bytes = total;
+  const bool want_out = out || d_out;
+  if (n_msgs > msg_cap) { ctx->err = "short_channel_ids replies: msg_off too small"; return LAMD_ERR_ARG; }
+  if (want_out && total > out_cap) { ctx->err = "short_channel_ids replies: output buffer too small"; return LAMD_ERR_ARG; }
+  if (msg_off) STCHK(hipMemcpyAsync(msg_off, d_msgoff, 8 * (n_msgs + 1), hipMemcpyDeviceToHost, st));
+  if (msg_rec && n_msgs) STCHK(hipMemcpyAsync(msg_rec, d_msgrec, 4 * n_msgs, hipMemcpyDeviceToHost, st));
+  if (want_out && n_msgs) {
+    if (!d_out && (rc = ensure(ctx, &ctx->store.sq_out, total + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+    u8 *d_bytes = d_out ? (u8 *)d_out : ctx->store.sq_out.as<u8>();
+    const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+    const store_sq_out ov{d_msgoff, d_msgrec, (u32)n_msgs, d_mfirst, (u32)nq, d_queries, d_qat, d_status};
+    hipLaunchKernelGGL(k_sq_encode, dim3((unsigned)((words + 255) / 256)), block, 0, st, words, dv, ov, d_bytes, total);
+    STCHK(hipGetLastError());
+    if (timed) STCHK(ctx->store.t_dig.record(4, st));
+    if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  }
+  STCHK(hipStreamSynchronize(st));   // the second wait: the offsets and the bytes
+  if (timed && want_out && n_msgs) {
+    float ms = 0;
+    STCHK(hipEventElapsedTime(&ms, ctx->store.t_dig.ev[3], ctx->store.t_dig.ev[4]));
+    summary->stage_ms[3] = ms;
+  }
   return LAMD_OK;
 }

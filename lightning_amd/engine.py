@@ -116,6 +116,46 @@ class StoreDigest:
         self.close()
 
 
+class StoreDirectory:
+    """lamd_store_directory: the directory Engine.gossip_store_directory built, resident on the device.  It refers to the image: a resident
+    d_store must stay alive until free().  free() it before its Engine."""
+
+    def __init__(self, engine, handle, summary, entries, bare, keep, chain_hash=None):
+        self._eng, self._h, self._entries, self._bare, self._keep = engine, handle, entries, bare, keep
+        self.chain_hash = None if chain_hash is None else bytes(chain_hash)
+        self.summary = {k: (list(getattr(summary, k)) if k == "stage_ms" else int(getattr(summary, k))) for k, _ in summary._fields_}
+
+    def __len__(self):
+        return int(self._eng._lib.lamd_store_directory_node_count(self._h)) if self._h else 0
+
+    def nodes(self):
+        """-> (id uint8 [nodes, 33], first uint32 [nodes], nann_rec uint32 [nodes] (0xFFFFFFFF: not announced)), in rank order"""
+        n = len(self)
+        ids, first, nann = np.zeros((max(1, n), 33), dtype=np.uint8), np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint32)
+        self._eng._chk(self._eng._lib.lamd_store_directory_read_nodes(self._h, n, ids.ctypes.data, first.ctypes.data, nann.ctypes.data))
+        return ids[:n], first[:n], nann[:n]
+
+    def channels(self):
+        """-> (bare_rec uint32 [bare], entry_rank uint32 [entries, 2], bare_rank uint32 [bare, 2] (0xFFFFFFFF: no node))"""
+        e, b = self._entries, self._bare
+        bare_rec, erank, brank = np.zeros(max(1, b), dtype=np.uint32), np.zeros((max(1, e), 2), dtype=np.uint32), np.zeros((max(1, b), 2), dtype=np.uint32)
+        self._eng._chk(self._eng._lib.lamd_store_directory_read_channels(self._h, e, b, bare_rec.ctypes.data, erank.ctypes.data, brank.ctypes.data))
+        return bare_rec[:b], erank[:e], brank[:b]
+
+    def free(self):
+        if self._h:
+            self._eng._lib.lamd_store_directory_free(self._h)
+            self._h = self._keep = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
 class Engine:
     """One context = one GPU, one stream.  Mirrors lamd_init()/lamd_shutdown()."""
 
@@ -552,6 +592,78 @@ class Engine:
         res = (status[:n], per_msg[:n], unknown[:s.unknown], stale[:s.stale], flags[:s.stale], messages)
         if return_summary:
             return res + ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
+
+    def gossip_store_directory(self, digest, blob=None, rec_off=None, verdict=None, d_store=None, chain_hash=None):
+        """lamd_gossip_store_directory_build: the directory of a gossip_store image, from the (image, rec_off, verdict) its StoreDigest was built
+        from and that digest: the records of every channel, the distinct node ids ranked by their 33 bytes, the node_announcement of each.  blob: the
+        image (copied to the device and owned by the directory), or d_store: the image in a torch uint8 CUDA tensor, read in place (the directory
+        keeps a reference to the tensor).  chain_hash: optional, the chain short_channel_ids_replies answers for by default.  -> StoreDirectory"""
+        if chain_hash is not None and len(bytes(chain_hash)) != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        if blob is None and d_store is None:
+            raise ValueError("an image on the host or on the device is needed")
+        buf_ptr, n_bytes = None, 0
+        if blob is not None:
+            _, n_bytes, buf = _store_blob(blob)
+            buf_ptr = buf.ctypes.data
+            if rec_off is None:
+                rec_off = gossip_store_frame(blob)[0]
+        if rec_off is None:
+            raise ValueError("a resident image needs rec_off")
+        d_ptr = None
+        if d_store is not None:
+            if blob is not None and d_store.numel() != n_bytes:
+                raise ValueError("the resident image and the host image differ in size")
+            n_bytes = d_store.numel()
+            self._after_torch()
+            d_ptr = d_store.data_ptr()
+        off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        v = None
+        if verdict is not None:
+            v = np.ascontiguousarray(verdict, dtype=np.int8)
+            if v.size != off.size:
+                raise ValueError("one verdict per record")
+        h, s = ctypes.c_void_p(), _ffi.LamdStoreDirectorySummary()
+        self._chk(self._lib.lamd_gossip_store_directory_build(self._ctx, buf_ptr, n_bytes, d_ptr, off.size, off.ctypes.data if off.size else None,
+                                                              v.ctypes.data if v is not None and v.size else None, digest._h, ctypes.byref(h), ctypes.byref(s)))
+        return StoreDirectory(self, h, s, len(digest), int(self._lib.lamd_store_digest_bare_count(digest._h)), d_store, chain_hash)
+
+    def short_channel_ids_replies(self, directory, queries, chain_hash=None, return_summary=False, return_records=False):
+        """lamd_short_channel_ids_reply_batch: the answers to a batch of raw query_short_channel_ids messages, from a StoreDirectory: per query
+        the stored channel_announcements and channel_updates its flags ask for, in the query's order, the node_announcements asked for, each
+        once, in the order of the node ids, and reply_short_channel_ids_end.  chain_hash: the 32 bytes of the chain this node serves
+        (default: the one given to gossip_store_directory).
+        -> (status int8 [queries] (0 answered, -1 malformed, 1 foreign chain: the end message alone, 2 bad flags, 3 bad scids, 4 flag count),
+        per_query uint32 [queries, 4] (scids, known, channel messages, node messages), [[bytes, ...], ...]); return_records: and per message the
+        record index it was copied from (0xFFFFFFFF: an end message)"""
+        if chain_hash is None:
+            chain_hash = directory.chain_hash
+        if chain_hash is None:
+            raise ValueError("a chain_hash is needed: here or at gossip_store_directory")
+        chain = np.frombuffer(bytes(chain_hash), dtype=np.uint8)
+        if chain.size != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        nq = len(queries)
+        qoff = np.zeros(nq + 1, dtype=np.uint64)
+        qoff[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(bytes(q) for q in queries) + b"\x00", dtype=np.uint8)
+        status, per_query, first = np.zeros(max(1, nq), dtype=np.int8), np.zeros((max(1, nq), 4), dtype=np.uint32), np.zeros(nq + 1, dtype=np.uint64)
+        s = _ffi.LamdScidReplySummary()
+        head = (self._ctx, directory._h, chain.ctypes.data, nq, blob.ctypes.data, qoff.ctypes.data, status.ctypes.data, per_query.ctypes.data, first.ctypes.data)
+        rc = self._lib.lamd_short_channel_ids_reply_batch(*head, 0, None, None, None, None, 0, ctypes.byref(s))          # the sizes
+        if rc < 0 and not (rc == -3 and s.messages):
+            self._chk(rc)
+        msg_off, msg_rec, out = np.zeros(s.messages + 1, dtype=np.uint64), np.zeros(max(1, s.messages), dtype=np.uint32), np.zeros(max(1, s.bytes), dtype=np.uint8)
+        self._chk(self._lib.lamd_short_channel_ids_reply_batch(*head, s.messages, msg_off.ctypes.data, msg_rec.ctypes.data, out.ctypes.data, None, s.bytes,
+                                                               ctypes.byref(s)))
+        raw = out.tobytes()
+        spans = [range(int(first[q]), int(first[q + 1])) for q in range(nq)]
+        res = (status[:nq], per_query[:nq], [[raw[int(msg_off[j]):int(msg_off[j + 1])] for j in sp] for sp in spans])
+        if return_records:
+            res += ([[int(msg_rec[j]) for j in sp] for sp in spans],)
+        if return_summary:
+            res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
         return res
 
     # ---- single-item veneers (reference semantics)
