@@ -768,6 +768,80 @@ int lamd_short_channel_ids_reply_batch(lamd_ctx *ctx, const lamd_store_directory
 				       size_t msg_cap, uint64_t *msg_off, uint32_t *msg_rec, uint8_t *out, void *d_out, size_t out_cap,
 				       lamd_scid_reply_summary *summary);
 
+/* ---- answering gossip_timestamp_filter from a store image: what handle_gossip_timestamp_filter_in() (connectd/multiplex.c:844-902) sets up
+ * and what maybe_gossip_msg() (:622-701) then sends, one gossmap_stream_next() (common/gossmap.c:1873-1981) per wakeup, for a batch of peers
+ * at once, as copies of the stored messages.
+ *
+ * THE STREAM INDEX is built from (image, rec_off, verdict) as a digest is and needs none.  Like the directory it REFERS TO THE IMAGE: a host
+ * `store` is copied to the device and owned by the index, a resident d_store is read in place and the caller keeps it alive until
+ * lamd_store_stream_free; rec_off is uploaded and kept.  Every device read stays inside the image whatever rec_off holds.  It is a snapshot:
+ * rebuild it after a repair.
+ *   STREAMABLE  record i, when the first of these that applies is none: its 12-byte header is not inside the image (skipped_frame); DELETED
+ *            (0x8000) is set (skipped_deleted); verdict is given and verdict[i] != LAMD_STORE_OK (skipped_verdict); DYING (0x0800) is set
+ *            (skipped_dying); its whole message is not inside the image or is shorter than 2 bytes (skipped_frame); its type is not 256,
+ *            257 or 258 (skipped_type).
+ *   THE LIST    the streamable records in file order, k = 0 .. count - 1: the record index, its HEADER timestamp, its message length; and
+ *            for every record i the number of streamable records in front of it.
+ *   RECENT(T)   the position in the list of the first streamable record at or behind the first record, of ANY type and whatever its
+ *            flags, whose header timestamp is >= T; count if there is none.  (gossmap_iter_fast_forward, gossmap.c:1984-2004, reads raw
+ *            headers only.  The reference moves one iterator forward once a minute; every record in front of it had a timestamp below
+ *            an older, smaller bound, so a search from the start finds the same record.)  Kept as the inclusive prefix maximum of all
+ *            records' header timestamps -- monotone, a record without a header inside the image adds 0 -- and found by bisection.
+ * Device work, on the context's stream: k_ts_flag (one lane per record: class, timestamps, length; the counters with one atomic per wave),
+ * rocPRIM's exclusive scan of the flags (n + 1 items) and inclusive max-scan of the timestamps, k_ts_compact (the list).  The call waits
+ * once, at its end, for the counters. */
+typedef struct lamd_store_stream lamd_store_stream;
+typedef struct {
+	uint64_t streamable;        /* the list's length */
+	uint64_t skipped_deleted, skipped_dying, skipped_type, skipped_verdict, skipped_frame;   /* the other records, by reason */
+	uint64_t bytes;             /* the streamable messages' lengths, summed */
+	double stage_ms[3];         /* with lamd_set_timing: flags, scans, compaction */
+} lamd_store_stream_summary;
+int lamd_gossip_store_stream_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
+				   const int8_t *verdict, lamd_store_stream **stream, lamd_store_stream_summary *summary);
+void lamd_store_stream_free(lamd_store_stream *stream);
+size_t lamd_store_stream_count(const lamd_store_stream *stream);
+/* the list: rec[cap], ts[cap], len[cap]; any may be NULL; cap < count: LAMD_ERR_ARG */
+int lamd_store_stream_read(const lamd_store_stream *stream, size_t cap, uint32_t *rec, uint32_t *ts, uint32_t *len);
+
+/* THE REPLIES.  Framing as lamd_short_channel_ids_reply_batch: the filter of peer p is filters + foff[p] .. foff[p + 1], its messages are
+ * reply_first[p] .. reply_first[p + 1] - 1, message j is out + msg_off[j] .. msg_off[j + 1]; msg_rec[j] (optional) is the record index
+ * the message was copied from.
+ * STATUS per peer, parsed on the host:
+ *   -1  not a gossip_timestamp_filter: shorter than 42 bytes, or type not 265.  Bytes behind the 42 are ignored (the generated fromwire_
+ *       returns cursor != NULL, tools/gen/impl_template:410).  No messages.
+ *    1  foreign chain_hash: no messages; the warning is the caller's.
+ *    0  streamed: min = first_timestamp, max = first_timestamp + timestamp_range - 1 in 32 bits, UINT32_MAX if that is below min.
+ *   A peer that is not streamed gets cursor_out = its cursor_in (UINT64_MAX with a NULL array) and done = 0: its stream is as it was.
+ * CURSOR  a position in the list, 0 .. count.  cursor_in[p] == UINT64_MAX, or a NULL array: "as the filter says" -- 0 for first_timestamp
+ *   0, count for 0xFFFFFFFF, else RECENT(now - 7200), the subtraction in 32 bits.  Any other value resumes there: the next wakeup of a
+ *   throttled peer.  A value above count: LAMD_ERR_ARG.
+ * THE WALK from the cursor, in list order: an entry PASSES if its header timestamp ts is 0 or min <= ts <= max.  A passing entry is taken
+ *   while the bytes taken so far are <= budget[p] (the check comes before the message, so the last one may overshoot); as soon as they
+ *   exceed it the walk stops, cursor_out = the last taken position + 1, done = 0.  When the list ends first: cursor_out = count, done = 1.
+ *   budget < 0: nothing is taken, cursor_out = the resolved start, done = 0.  A NULL budget: unlimited.
+ *   The per-peer state -- gossip_rcvd_filter, the 60-second timer, dev_suppress_gossip -- and the warnings' text are the caller's.
+ * SIZES  as lamd_short_channel_ids_reply_batch: msg_cap must hold the messages, out_cap the bytes (when out or d_out is given).  One too
+ *   small: LAMD_ERR_ARG with summary, status, cursor_out, done and reply_first filled in and nothing written to msg_off, msg_rec, out or
+ *   d_out.  All caps 0: the sizes alone.  The bytes go to out (host), d_out (device, any alignment), or neither.
+ * Device work, on the context's stream: k_tf_select, ONE WAVEFRONT per peer in a one-wave workgroup, walks the list from the cursor in
+ * tiles of 64 entries -- coalesced loads of timestamps and lengths, the predicate as a ballot mask, a wave-wide inclusive scan of the
+ * passing lengths with cross-lane shuffles, the 64-bit byte total carried across tiles, a stop test that is uniform across the wave, each
+ * taken entry's slot from the popcount of the mask below its lane.  It runs twice: a counting pass (messages, bytes, cursor_out, done),
+ * k_range_scan over the peers, then, behind the first wait, the writing pass over the same tiles (msg_rec, msg_off) and k_sq_encode,
+ * one aligned 32-bit word of the output per lane.  The host waits once for the sizes and once for the bytes; no host round trip inside
+ * the walk.  Limits: np and the messages of one call below UINT32_MAX, foff non-decreasing, the index built by this context. */
+typedef struct {
+	uint64_t by_status[3];   /* peers: [0] streamed, [1] foreign chain, [2] malformed */
+	uint64_t messages, bytes;   /* what msg_cap and out_cap must hold */
+	uint64_t finished;       /* peers with done = 1 */
+	double stage_ms[4];      /* with lamd_set_timing: count, scan, write, encode */
+} lamd_filter_reply_summary;
+int lamd_timestamp_filter_reply_batch(lamd_ctx *ctx, const lamd_store_stream *stream, const uint8_t *chain_hash32, uint32_t now, size_t np,
+				      const uint8_t *filters, const uint64_t *foff, const uint64_t *cursor_in, const int64_t *budget, int8_t *status,
+				      uint64_t *cursor_out, uint8_t *done, uint64_t *reply_first, size_t msg_cap, uint64_t *msg_off,
+				      uint32_t *msg_rec, uint8_t *out, void *d_out, size_t out_cap, lamd_filter_reply_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

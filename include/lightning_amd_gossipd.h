@@ -24,7 +24,9 @@
  * (prune_network) and dying / spent channels (channel_spent, new_block).  What is not: compaction, the seeker, local (known_amount)
  * announcements, and the peers' queries (query_channel_range is answered from a store image by lamd_channel_range_reply_batch and the
  * seeker's comparison of peers' reply_channel_range with the store is lamd_channel_range_compare_batch, include/lightning_amd.h; the
- * query_short_channel_ids responder and gossip_timestamp_filter are not built) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
+ * query_short_channel_ids responder is lamd_short_channel_ids_reply_batch and a peer's gossip_timestamp_filter is answered by
+ * lamd_timestamp_filter_reply_batch, both from the same image; the per-peer state of a stream -- gossip_rcvd_filter, the 60-second
+ * timer, dev_suppress_gossip -- stays with the caller) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
  * append to / delete from / re-flag the store) and it does the I/O.
  *
  * Everything observable is reported through the event callback, in the order the reference would produce it; texts

@@ -85,6 +85,18 @@ class LamdScidReplySummary(ctypes.Structure):
                 ("stage_ms", ctypes.c_double * 4)]
 
 
+class LamdStoreStreamSummary(ctypes.Structure):
+    """lamd_store_stream_summary (include/lightning_amd.h): what lamd_gossip_store_stream_build reports about the stream index it built"""
+    _fields_ = [("streamable", ctypes.c_uint64), ("skipped_deleted", ctypes.c_uint64), ("skipped_dying", ctypes.c_uint64), ("skipped_type", ctypes.c_uint64),
+                ("skipped_verdict", ctypes.c_uint64), ("skipped_frame", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
+
+
+class LamdFilterReplySummary(ctypes.Structure):
+    """lamd_filter_reply_summary (include/lightning_amd.h): what lamd_timestamp_filter_reply_batch reports about a batch of peers"""
+    _fields_ = [("by_status", ctypes.c_uint64 * 3), ("messages", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("finished", ctypes.c_uint64),
+                ("stage_ms", ctypes.c_double * 4)]
+
+
 class LamdGtableAuditResult(ctypes.Structure):
     """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
     _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
@@ -158,6 +170,13 @@ SYMBOLS = {
     "lamd_store_directory_read_channels": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_sz, c_u8p, c_u8p, c_u8p]),
     "lamd_short_channel_ids_reply_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p,
                                                           ctypes.c_void_p, c_sz, ctypes.POINTER(LamdScidReplySummary)]),
+    "lamd_gossip_store_stream_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_sz, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_void_p),
+                                                      ctypes.POINTER(LamdStoreStreamSummary)]),
+    "lamd_store_stream_free": (None, [ctypes.c_void_p]),
+    "lamd_store_stream_count": (c_sz, [ctypes.c_void_p]),
+    "lamd_store_stream_read": (ctypes.c_int, [ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p]),
+    "lamd_timestamp_filter_reply_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p,
+                                                         c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, ctypes.c_void_p, c_sz, ctypes.POINTER(LamdFilterReplySummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

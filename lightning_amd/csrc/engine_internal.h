@@ -196,9 +196,9 @@ struct lamd_ctx {
   // range comparison: the peers' messages, classes, lists, the sorts' workspace, and the queries it writes; directory build: candidates, keys,
   // permutations, the sorts' workspace; short_channel_ids replies: the queries, per-occurrence and per-node arrays, offsets, and the messages.
   // t_audit / t_rep: the stage boundaries of an audit and of a repair's own stages; t_dig: those of a digest or directory build, a range reply, a
-  // comparison or a short_channel_ids reply
+  // comparison, a short_channel_ids reply, a stream index build or a timestamp filter reply
   struct store_ws {
-    devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out, dir, sq, sq_out;
+    devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out, dir, sq, sq_out, ts, ts_msg, ts_out;
     stage_timer<6> t_audit;
     stage_timer<4> t_rep;
     stage_timer<6> t_dig;

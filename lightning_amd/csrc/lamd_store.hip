@@ -1,5 +1,5 @@
 // liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies, the comparison of peers' replies,
-// the directory of an image and the answers to query_short_channel_ids
+// the directory of an image and the answers to query_short_channel_ids, the stream index of an image and the answers to gossip_timestamp_filter
 #include "engine_internal.h"
 #include "store_audit.h"
 #include "store_repair.h"
@@ -7,6 +7,7 @@
 #include "store_digest.h"
 #include "store_compare.h"
 #include "store_query.h"
+#include "store_stream.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <memory>
@@ -1640,6 +1641,327 @@ extern "C" int lamd_short_channel_ids_reply_batch(lamd_ctx *ctx, const lamd_stor
     float ms = 0;
     STCHK(hipEventElapsedTime(&ms, ctx->store.t_dig.ev[3], ctx->store.t_dig.ev[4]));
     summary->stage_ms[3] = ms;
+  }
+  return LAMD_OK;
+}
+
+// ---- the stream index of a store image (lamd_gossip_store_stream_build; per-record logic in store_stream.h).  cnt: one word per
+// STORE_STREAM_* class, all 0; bytes: the streamable messages' lengths, 0.
+// k_ts_flag: one lane per record and one that closes the flags: flag[n + 1], the header timestamp of every record, timestamp and length of the streamable ones
+__global__ void __launch_bounds__(256) k_ts_flag(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                 const int8_t *__restrict__ verdict, u32 *__restrict__ flag, u32 *__restrict__ hts, u32 *__restrict__ tts,
+                                                 u32 *__restrict__ tlen, u32 *cnt, unsigned long long *bytes) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  u32 cls = STORE_STREAM_CLASSES, h = 0, ts = 0, len = 0;
+  if (i < n) {
+    cls = store_stream_class(store, store_len, rec_off, verdict, i, &h, &ts, &len);
+    flag[i] = cls == STORE_STREAM_OK;
+    hts[i] = h;
+    tts[i] = ts;
+    tlen[i] = len;
+  } else if (i == n) {
+    flag[n] = 0;
+  }
+  for (u32 c = 0; c < STORE_STREAM_CLASSES; c++) wave_count(&cnt[c], cls == c);
+  u32 w = len;   // 64 lengths of 16 bits
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o, 64);
+  if ((threadIdx.x & 63u) == 0 && w) atomicAdd(bytes, (unsigned long long)w);
+}
+// k_ts_compact: one lane per record; spos: the exclusive scan of the flags
+__global__ void __launch_bounds__(256) k_ts_compact(u32 n, const u32 *__restrict__ flag, const u32 *__restrict__ spos, const u32 *__restrict__ tts,
+                                                    const u32 *__restrict__ tlen, u32 *__restrict__ srec, u32 *__restrict__ sts, u32 *__restrict__ slen) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const u32 k = spos[i];   // < n: at most i streamable records lie in front of record i
+  srec[k] = i;
+  sts[k] = tts[i];
+  slen[k] = tlen[i];
+}
+
+struct lamd_store_stream {
+  lamd_ctx *ctx = nullptr;
+  void *mem = nullptr;          // rec_off u64[n] | spos u32[n + 1] | pmax, srec, sts, slen u32[n] each | the image, unless it is the caller's
+  const u8 *img = nullptr;      // the image on the device: inside mem, or the caller's d_store
+  size_t img_len = 0, n = 0, count = 0;
+  u64 *rec_off = nullptr;
+  u32 *spos = nullptr, *pmax = nullptr, *srec = nullptr, *sts = nullptr, *slen = nullptr;
+  store_tf_index view() const { return store_tf_index{srec, sts, slen, spos, pmax, (u32)n, (u32)count}; }
+};
+extern "C" void lamd_store_stream_free(lamd_store_stream *s) {
+  if (!s) return;
+  if (s->mem) {
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipFree(s->mem);
+  }
+  delete s;
+}
+extern "C" size_t lamd_store_stream_count(const lamd_store_stream *s) { return s ? s->count : 0; }
+extern "C" int lamd_store_stream_read(const lamd_store_stream *s, size_t cap, uint32_t *rec, uint32_t *ts, uint32_t *len) {
+  if (!s) return LAMD_ERR_ARG;
+  lamd_ctx *ctx = s->ctx;
+  if (cap < s->count) { ctx->err = "gossip_store stream: arrays too small"; return LAMD_ERR_ARG; }
+  if (s->count == 0) return LAMD_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (rec) HIPCHK(ctx, hipMemcpy(rec, s->srec, 4 * s->count, hipMemcpyDeviceToHost));
+  if (ts) HIPCHK(ctx, hipMemcpy(ts, s->sts, 4 * s->count, hipMemcpyDeviceToHost));
+  if (len) HIPCHK(ctx, hipMemcpy(len, s->slen, 4 * s->count, hipMemcpyDeviceToHost));
+  return LAMD_OK;
+}
+extern "C" int lamd_gossip_store_stream_build(lamd_ctx *ctx, const uint8_t *store, size_t len, const void *d_store, size_t n, const uint64_t *rec_off,
+                                              const int8_t *verdict, lamd_store_stream **stream, lamd_store_stream_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (stream) *stream = nullptr;
+  if ((!store && !d_store) || !stream || !summary || (n && !rec_off) || n >= (size_t)STORE_NONE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_store_stream_summary();
+  std::unique_ptr<lamd_store_stream, void (*)(lamd_store_stream *)> S(new (std::nothrow) lamd_store_stream(), lamd_store_stream_free);
+  if (!S) return LAMD_ERR_NOMEM;
+  S->ctx = ctx;
+  S->n = n;
+  S->img_len = len;
+  lamd_ctx *L = ctx;   // queued copies read the caller's arrays: an error return drains the stream (drain_fail), then the index frees itself
+  hipStream_t st = ctx->stream;
+  const size_t o_img = 8 * n + 4 * (5 * n + 2);
+  hipError_t e0 = hipSetDevice(ctx->device);
+  if (e0 == hipSuccess) e0 = hipMalloc(&S->mem, o_img + (d_store ? 0 : len) + 16);
+  if (e0 != hipSuccess) {
+    ctx->err = std::string("gossip_store stream: ") + hipGetErrorString(e0);
+    return drain_fail(ctx, L, e0 == hipErrorOutOfMemory ? LAMD_ERR_NOMEM : LAMD_ERR_HIP);
+  }
+  S->rec_off = (u64 *)S->mem;
+  S->spos = (u32 *)(S->rec_off + n);
+  S->pmax = S->spos + n + 1;
+  S->srec = S->pmax + n;
+  S->sts = S->srec + n;
+  S->slen = S->sts + n;
+  S->img = d_store ? (const u8 *)d_store : (const u8 *)S->mem + o_img;
+  if (n == 0) {   // an empty list: spos[0] = 0 is all a walk reads
+    STCHK(hipMemsetAsync(S->spos, 0, 4, st));
+    STCHK(hipStreamSynchronize(st));
+    *stream = S.release();
+    return LAMD_OK;
+  }
+  size_t tmp_bytes = 0, need = 0;
+  STCHK(rocprim::exclusive_scan(nullptr, tmp_bytes, (const u32 *)nullptr, (u32 *)nullptr, (u32)0, n + 1, rocprim::plus<u32>(), st));
+  STCHK(rocprim::inclusive_scan(nullptr, need, (const u32 *)nullptr, (u32 *)nullptr, n, rocprim::maximum<u32>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  // bytes u64 | cnt u32[8] | flag u32[n + 1] | hts, tts, tlen u32[n] each | verdict i8[n] | (256-aligned) the scans' workspace
+  const size_t o_tmp = align_up(8 + 32 + 4 * (4 * n + 1) + n, 256);
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.ts, o_tmp + tmp_bytes + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_dig.create());
+  unsigned long long *d_bytes = ctx->store.ts.as<unsigned long long>();
+  u32 *d_cnt = (u32 *)(d_bytes + 1), *d_flag = d_cnt + 8, *d_hts = d_flag + n + 1, *d_tts = d_hts + n, *d_tlen = d_tts + n;
+  int8_t *d_verdict = verdict ? (int8_t *)(d_tlen + n) : nullptr;
+  void *d_tmp = ctx->store.ts.as<u8>() + o_tmp;
+  const u8 *img = S->img;
+  if (!d_store) STCHK(hipMemcpyAsync((void *)img, store, len, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(S->rec_off, rec_off, 8 * n, hipMemcpyHostToDevice, st));
+  if (verdict) STCHK(hipMemcpyAsync(d_verdict, verdict, n, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(d_bytes, 0, 8 + 32, st));
+  const dim3 block(256);
+  if (timed) STCHK(ctx->store.t_dig.record(0, st));
+  hipLaunchKernelGGL(k_ts_flag, dim3(blocks_for(n + 1)), block, 0, st, (u32)n, img, len, (const u64 *)S->rec_off, (const int8_t *)d_verdict, d_flag, d_hts, d_tts, d_tlen,
+                     d_cnt, d_bytes);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(1, st));
+  STCHK(rocprim::exclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_flag, S->spos, (u32)0, n + 1, rocprim::plus<u32>(), st));
+  STCHK(rocprim::inclusive_scan(d_tmp, tmp_bytes, (const u32 *)d_hts, S->pmax, n, rocprim::maximum<u32>(), st));
+  if (timed) STCHK(ctx->store.t_dig.record(2, st));
+  hipLaunchKernelGGL(k_ts_compact, dim3(blocks_for(n)), block, 0, st, (u32)n, (const u32 *)d_flag, (const u32 *)S->spos, (const u32 *)d_tts, (const u32 *)d_tlen, S->srec,
+                     S->sts, S->slen);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(3, st));
+  struct { unsigned long long bytes; u32 cnt[8]; } h = {};
+  static_assert(sizeof h == 40, "bytes, then the counters");
+  STCHK(hipMemcpyAsync(&h, d_bytes, sizeof h, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  if (timed) STCHK(ctx->store.t_dig.read(3, summary->stage_ms));
+  S->count = h.cnt[STORE_STREAM_OK];
+  summary->streamable = h.cnt[STORE_STREAM_OK];
+  summary->skipped_deleted = h.cnt[STORE_STREAM_DELETED];
+  summary->skipped_dying = h.cnt[STORE_STREAM_DYING];
+  summary->skipped_type = h.cnt[STORE_STREAM_TYPE];
+  summary->skipped_verdict = h.cnt[STORE_STREAM_VERDICT];
+  summary->skipped_frame = h.cnt[STORE_STREAM_FRAME];
+  summary->bytes = h.bytes;
+  *stream = S.release();
+  return LAMD_OK;
+}
+
+// ---- gossip_timestamp_filter answers (lamd_timestamp_filter_reply_batch; per-peer and per-tile logic in store_stream.h).
+// k_tf_select: ONE WAVE per peer, in a workgroup of its own.  WRITE false: the counting pass leaves n_msgs, n_bytes, cursor_out, done.
+// WRITE true: the same tiles again; the taken entries go to msg_rec / msg_off behind msg_first[p] / byte_first[p] (below n_total, which
+// the counting pass found), the last peer's wave closes msg_off with the total.
+template <bool WRITE>
+__global__ void __launch_bounds__(64) k_tf_select(u32 np, const store_tf_peer *__restrict__ peers, u32 now, store_tf_index x, u32 *__restrict__ n_msgs,
+                                                  u64 *__restrict__ n_bytes, u64 *__restrict__ cursor_out, u8 *__restrict__ done,
+                                                  const u64 *__restrict__ msg_first, const u64 *__restrict__ byte_first, u64 n_total,
+                                                  u64 *__restrict__ msg_off, u32 *__restrict__ msg_rec) {
+  const u32 p = blockIdx.x, lane = threadIdx.x;
+  if (p >= np) return;   // (the whole wave)
+  const store_tf_peer pe = peers[p];
+  if (WRITE && p == np - 1 && lane == 0) msg_off[n_total] = byte_first[np];
+  u64 cur = pe.cursor, bytes = 0;
+  u32 msgs = 0, fin = 0;
+  if (pe.status == STORE_TF_STREAMED) {
+    cur = store_tf_start(x, pe, now);
+    if (cur > x.n_stream) cur = x.n_stream;   // (never: the host checked the cursors)
+    if (pe.budget >= 0) {
+      const u64 m0 = WRITE ? msg_first[p] : 0, b0 = WRITE ? byte_first[p] : 0;
+      // cur, bytes, msgs and every branch below are uniform across the wave.  The loads of the next tile are issued in front of the work on
+      // this one, and a tile nothing of which passes costs a ballot: a narrow filter walks a long list at the speed of its loads.
+      u64 k = cur + lane;
+      bool in = k < x.n_stream;
+      u32 ts = in ? x.sts[k] : 0, len = in ? x.slen[k] : 0;
+      for (;;) {
+        if (cur >= x.n_stream) { cur = x.n_stream; fin = 1; break; }
+        const u64 k_next = k + 64;
+        const bool in_next = k_next < x.n_stream;
+        const u32 ts_next = in_next ? x.sts[k_next] : 0, len_next = in_next ? x.slen[k_next] : 0;
+        const bool pass = in && store_tf_pass(ts, pe.min, pe.max);
+        const u64 pm = __ballot(pass);
+        if (pm) {
+          u32 incl = pass ? len : 0;   // 64 lengths of 16 bits
+#pragma unroll
+          for (int d = 1; d < 64; d <<= 1) {
+            const u32 t = __shfl_up(incl, d, 64);
+            if ((int)lane >= d) incl += t;
+          }
+          const u64 sm = __ballot(store_tf_stops(pass, bytes, incl, pe.budget)), take = store_tf_taken(pm, sm);
+          if (WRITE && ((take >> lane) & 1)) {
+            const u64 slot = m0 + msgs + (u32)__popcll(take & ((1ull << lane) - 1ull));
+            if (slot < n_total) {
+              msg_rec[slot] = x.srec[k];
+              msg_off[slot] = b0 + bytes + incl - len;
+            }
+          }
+          msgs += (u32)__popcll(take);
+          const u32 last = sm ? store_tf_first_lane(sm) : 63u;
+          bytes += (u32)__builtin_amdgcn_readfirstlane((int)__shfl(incl, (int)last, 64));
+          if (sm) { cur += last + 1; break; }
+        }
+        cur += 64;
+        k = k_next;
+        in = in_next;
+        ts = ts_next;
+        len = len_next;
+      }
+    }
+  }
+  if (!WRITE && lane == 0) {
+    n_msgs[p] = msgs;
+    n_bytes[p] = bytes;
+    cursor_out[p] = cur;
+    done[p] = (u8)fin;
+  }
+}
+
+extern "C" int lamd_timestamp_filter_reply_batch(lamd_ctx *ctx, const lamd_store_stream *stream, const uint8_t *chain_hash32, uint32_t now, size_t np,
+                                                 const uint8_t *filters, const uint64_t *foff, const uint64_t *cursor_in, const int64_t *budget, int8_t *status,
+                                                 uint64_t *cursor_out, uint8_t *done, uint64_t *reply_first, size_t msg_cap, uint64_t *msg_off,
+                                                 uint32_t *msg_rec, uint8_t *out, void *d_out, size_t out_cap, lamd_filter_reply_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!stream || stream->ctx != ctx || !chain_hash32 || !summary || !reply_first || (np && (!filters || !foff || !status || !cursor_out || !done)) ||
+      (msg_cap && !msg_off) || np >= (size_t)STORE_NONE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_filter_reply_summary();
+  reply_first[0] = 0;
+  if (np == 0) {
+    if (msg_cap) msg_off[0] = 0;
+    return LAMD_OK;
+  }
+  // the framing, on the host: status, bounds and start rule of every peer
+  std::vector<store_tf_peer> peers(np);
+  for (size_t p = 0; p < np; p++) {
+    if (foff[p + 1] < foff[p]) { ctx->err = "timestamp filter replies: decreasing filter offsets"; return LAMD_ERR_ARG; }
+    const u64 c = cursor_in ? cursor_in[p] : STORE_TF_AS_FILTER;
+    if (c != STORE_TF_AS_FILTER && c > stream->count) { ctx->err = "timestamp filter replies: a cursor behind the end of the list"; return LAMD_ERR_ARG; }
+    const store_tf_filter f = store_tf_parse(filters + foff[p], (size_t)(foff[p + 1] - foff[p]), chain_hash32);
+    peers[p] = store_tf_peer{f.status, f.min, f.max, f.rule, c, budget ? budget[p] : INT64_MAX};
+  }
+  for (size_t p = 0; p < np; p++) {
+    status[p] = (int8_t)peers[p].status;
+    summary->by_status[peers[p].status < 0 ? 2 : peers[p].status]++;
+  }
+  lamd_ctx *L = ctx;   // queued copies read this frame's vectors: STCHK drains the stream
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // peers store_tf_peer[np] | n_bytes u64[np] | msg_first, byte_first u64[np + 1] each | cursor_out u64[np] | n_msgs u32[np] | done u8[np]
+  static_assert(sizeof(store_tf_peer) == 32, "the peers lie in front of 8-byte words");
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.ts, 32 * np + 8 * (4 * np + 2) + 4 * np + np + 16)) != LAMD_OK) return rc;
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_dig.create());
+  store_tf_peer *d_peers = ctx->store.ts.as<store_tf_peer>();
+  u64 *d_nbytes = (u64 *)(d_peers + np), *d_mfirst = d_nbytes + np, *d_bfirst = d_mfirst + np + 1, *d_cur = d_bfirst + np + 1;
+  u32 *d_nmsgs = (u32 *)(d_cur + np);
+  u8 *d_done = (u8 *)(d_nmsgs + np);
+  std::vector<u64> h_first(2 * (np + 1));
+  STCHK(hipMemcpyAsync(d_peers, peers.data(), 32 * np, hipMemcpyHostToDevice, st));
+  const store_tf_index xv = stream->view();
+  const dim3 wave(64), grid((unsigned)np);
+  if (timed) STCHK(ctx->store.t_dig.record(0, st));
+  hipLaunchKernelGGL(k_tf_select<false>, grid, wave, 0, st, (u32)np, (const store_tf_peer *)d_peers, now, xv, d_nmsgs, d_nbytes, d_cur, d_done, (const u64 *)nullptr,
+                     (const u64 *)nullptr, (u64)0, (u64 *)nullptr, (u32 *)nullptr);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(1, st));
+  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(256), 0, st, (u32)np, (const u32 *)d_nmsgs, (const u64 *)d_nbytes, d_mfirst, d_bfirst);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(2, st));
+  STCHK(hipMemcpyAsync(h_first.data(), d_mfirst, 16 * (np + 1), hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(cursor_out, d_cur, 8 * np, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(done, d_done, np, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: sizes, cursors and done flags
+  if (timed) STCHK(ctx->store.t_dig.read(2, summary->stage_ms));
+  const u64 n_msgs = h_first[np], total = h_first[2 * np + 1];
+  memcpy(reply_first, h_first.data(), 8 * (np + 1));
+  for (size_t p = 0; p < np; p++) summary->finished += done[p];
+  summary->messages = n_msgs;
+  summary->bytes = total;
+  const bool want_out = out || d_out;
+  if (n_msgs >= (u64)STORE_NONE) { ctx->err = "timestamp filter replies: too many messages for one call"; return LAMD_ERR_ARG; }
+  if (n_msgs > msg_cap) { ctx->err = "timestamp filter replies: msg_off too small"; return LAMD_ERR_ARG; }
+  if (want_out && total > out_cap) { ctx->err = "timestamp filter replies: output buffer too small"; return LAMD_ERR_ARG; }
+  if (!msg_off && !(want_out && n_msgs)) return LAMD_OK;
+  // msg_off u64[n_msgs + 1] | msg_rec u32[n_msgs]
+  if ((rc = ensure(ctx, &ctx->store.ts_msg, 12 * n_msgs + 8 + 16)) != LAMD_OK) return rc;
+  u64 *d_msgoff = ctx->store.ts_msg.as<u64>();
+  u32 *d_msgrec = (u32 *)(d_msgoff + n_msgs + 1);
+  if (timed) STCHK(ctx->store.t_dig.record(3, st));
+  hipLaunchKernelGGL(k_tf_select<true>, grid, wave, 0, st, (u32)np, (const store_tf_peer *)d_peers, now, xv, (u32 *)nullptr, (u64 *)nullptr, (u64 *)nullptr, (u8 *)nullptr,
+                     (const u64 *)d_mfirst, (const u64 *)d_bfirst, n_msgs, d_msgoff, d_msgrec);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_dig.record(4, st));
+  if (msg_off) STCHK(hipMemcpyAsync(msg_off, d_msgoff, 8 * (n_msgs + 1), hipMemcpyDeviceToHost, st));
+  if (msg_rec && n_msgs) STCHK(hipMemcpyAsync(msg_rec, d_msgrec, 4 * n_msgs, hipMemcpyDeviceToHost, st));
+  if (want_out && n_msgs) {
+    if (!d_out && (rc = ensure(ctx, &ctx->store.ts_out, total + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+    u8 *d_bytes = d_out ? (u8 *)d_out : ctx->store.ts_out.as<u8>();
+    const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+    // every message is the copy of a record: the encoder of the short_channel_ids replies, with a directory that holds the image alone
+    const store_sq_dir dv{stream->img, stream->img_len, stream->rec_off, (u32)stream->n, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0};
+    const store_sq_out ov{d_msgoff, d_msgrec, (u32)n_msgs, d_mfirst, (u32)np, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL(k_sq_encode, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, words, dv, ov, d_bytes, total);
+    STCHK(hipGetLastError());
+    if (timed) STCHK(ctx->store.t_dig.record(5, st));
+    if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  }
+  STCHK(hipStreamSynchronize(st));   // the second wait: the offsets and the bytes
+  if (timed) {
+    float ms = 0;
+    STCHK(hipEventElapsedTime(&ms, ctx->store.t_dig.ev[3], ctx->store.t_dig.ev[4]));
+    summary->stage_ms[2] = ms;
+    if (want_out && n_msgs) {
+      STCHK(hipEventElapsedTime(&ms, ctx->store.t_dig.ev[4], ctx->store.t_dig.ev[5]));
+      summary->stage_ms[3] = ms;
+    }
   }
   return LAMD_OK;
 }

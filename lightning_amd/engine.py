@@ -156,6 +156,38 @@ class StoreDirectory:
         self.free()
 
 
+class StoreStream:
+    """lamd_store_stream: the stream index Engine.gossip_store_stream built, resident on the device: the records gossmap_stream_next would hand
+    out, in file order.  It refers to the image: a resident d_store must stay alive until free().  free() it before its Engine."""
+
+    def __init__(self, engine, handle, summary, keep):
+        self._eng, self._h, self._keep = engine, handle, keep
+        self.summary = {k: (list(getattr(summary, k)) if k == "stage_ms" else int(getattr(summary, k))) for k, _ in summary._fields_}
+
+    def __len__(self):
+        return int(self._eng._lib.lamd_store_stream_count(self._h)) if self._h else 0
+
+    def read(self):
+        """-> (rec uint32 [count] (the record index), ts uint32 [count] (its header timestamp), len uint32 [count] (its message length)), in file order"""
+        n = len(self)
+        rec, ts, ln = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint32)
+        self._eng._chk(self._eng._lib.lamd_store_stream_read(self._h, n, rec.ctypes.data, ts.ctypes.data, ln.ctypes.data))
+        return rec[:n], ts[:n], ln[:n]
+
+    def free(self):
+        if self._h:
+            self._eng._lib.lamd_store_stream_free(self._h)
+            self._h = self._keep = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
 class Engine:
     """One context = one GPU, one stream.  Mirrors lamd_init()/lamd_shutdown()."""
 
@@ -660,6 +692,84 @@ class Engine:
         raw = out.tobytes()
         spans = [range(int(first[q]), int(first[q + 1])) for q in range(nq)]
         res = (status[:nq], per_query[:nq], [[raw[int(msg_off[j]):int(msg_off[j + 1])] for j in sp] for sp in spans])
+        if return_records:
+            res += ([[int(msg_rec[j]) for j in sp] for sp in spans],)
+        if return_summary:
+            res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
+
+    def gossip_store_stream(self, blob=None, rec_off=None, verdict=None, d_store=None):
+        """lamd_gossip_store_stream_build: the stream index of a gossip_store image: the records a peer's gossip_timestamp_filter can be answered
+        with (DELETED and DYING clear, verdict OK where verdicts are given, type 256, 257 or 258, inside the image), in file order, with their
+        header timestamps and lengths, and the prefix maximum of all header timestamps for the "recent" position.  blob: the image (copied to the
+        device and owned by the index), or d_store: the image in a torch uint8 CUDA tensor, read in place (the index keeps a reference to the
+        tensor).  A snapshot: build it again after a repair.  -> StoreStream"""
+        if blob is None and d_store is None:
+            raise ValueError("an image on the host or on the device is needed")
+        buf_ptr, n_bytes = None, 0
+        if blob is not None:
+            _, n_bytes, buf = _store_blob(blob)
+            buf_ptr = buf.ctypes.data
+            if rec_off is None:
+                rec_off = gossip_store_frame(blob)[0]
+        if rec_off is None:
+            raise ValueError("a resident image needs rec_off")
+        d_ptr = None
+        if d_store is not None:
+            if blob is not None and d_store.numel() != n_bytes:
+                raise ValueError("the resident image and the host image differ in size")
+            n_bytes = d_store.numel()
+            self._after_torch()
+            d_ptr = d_store.data_ptr()
+        off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        v = None
+        if verdict is not None:
+            v = np.ascontiguousarray(verdict, dtype=np.int8)
+            if v.size != off.size:
+                raise ValueError("one verdict per record")
+        h, s = ctypes.c_void_p(), _ffi.LamdStoreStreamSummary()
+        self._chk(self._lib.lamd_gossip_store_stream_build(self._ctx, buf_ptr, n_bytes, d_ptr, off.size, off.ctypes.data if off.size else None,
+                                                           v.ctypes.data if v is not None and v.size else None, ctypes.byref(h), ctypes.byref(s)))
+        return StoreStream(self, h, s, d_store)
+
+    def timestamp_filter_replies(self, stream, filters, chain_hash, now, cursors=None, budgets=None, return_summary=False, return_records=False):
+        """lamd_timestamp_filter_reply_batch: what a batch of peers that sent raw gossip_timestamp_filter messages are streamed from a StoreStream.
+        chain_hash: the 32 bytes of the chain this node serves; now: the clock in seconds (the "recent" position is the first record stamped
+        now - 7200 or later); cursors: per peer a position in the list to resume at, or None / 2**64 - 1: where the filter says (the start for
+        first_timestamp 0, the end for 0xFFFFFFFF, else the recent position); budgets: per peer the bytes it may be sent in this call (a message
+        is sent while the bytes so far are <= budget; < 0: nothing), None: unlimited.
+        -> (status int8 [peers] (0 streamed, -1 malformed, 1 foreign chain), cursor_out uint64 [peers], done uint8 [peers] (1: the list ended),
+        [[bytes, ...], ...]); return_records: and per message the record index it was copied from"""
+        chain = np.frombuffer(bytes(chain_hash), dtype=np.uint8)
+        if chain.size != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        n = len(filters)
+        foff = np.zeros(n + 1, dtype=np.uint64)
+        foff[1:] = np.cumsum([len(f) for f in filters], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(bytes(f) for f in filters) + b"\x00", dtype=np.uint8)
+        cur = bud = None
+        if cursors is not None:
+            if len(cursors) != n:
+                raise ValueError("one cursor per peer")
+            cur = np.array([2 ** 64 - 1 if c is None else int(c) for c in cursors] + [0], dtype=np.uint64)
+        if budgets is not None:
+            if len(budgets) != n:
+                raise ValueError("one budget per peer")
+            bud = np.array([2 ** 63 - 1 if b is None else int(b) for b in budgets] + [0], dtype=np.int64)
+        status, cursor_out, done, first = (np.zeros(max(1, n), dtype=np.int8), np.zeros(max(1, n), dtype=np.uint64), np.zeros(max(1, n), dtype=np.uint8),
+                                           np.zeros(n + 1, dtype=np.uint64))
+        s = _ffi.LamdFilterReplySummary()
+        head = (self._ctx, stream._h, chain.ctypes.data, int(now) & 0xFFFFFFFF, n, blob.ctypes.data, foff.ctypes.data, None if cur is None else cur.ctypes.data,
+                None if bud is None else bud.ctypes.data, status.ctypes.data, cursor_out.ctypes.data, done.ctypes.data, first.ctypes.data)
+        rc = self._lib.lamd_timestamp_filter_reply_batch(*head, 0, None, None, None, None, 0, ctypes.byref(s))          # the sizes
+        if rc < 0 and not (rc == -3 and s.messages):
+            self._chk(rc)
+        msg_off, msg_rec, out = np.zeros(s.messages + 1, dtype=np.uint64), np.zeros(max(1, s.messages), dtype=np.uint32), np.zeros(max(1, s.bytes), dtype=np.uint8)
+        self._chk(self._lib.lamd_timestamp_filter_reply_batch(*head, s.messages, msg_off.ctypes.data, msg_rec.ctypes.data, out.ctypes.data, None, s.bytes,
+                                                              ctypes.byref(s)))
+        raw = out.tobytes()
+        spans = [range(int(first[p]), int(first[p + 1])) for p in range(n)]
+        res = (status[:n], cursor_out[:n], done[:n], [[raw[int(msg_off[j]):int(msg_off[j + 1])] for j in sp] for sp in spans])
         if return_records:
             res += ([[int(msg_rec[j]) for j in sp] for sp in spans],)
         if return_summary:
