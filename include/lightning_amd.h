@@ -842,6 +842,78 @@ int lamd_timestamp_filter_reply_batch(lamd_ctx *ctx, const lamd_store_stream *st
 				      uint64_t *cursor_out, uint8_t *done, uint64_t *reply_first, size_t msg_cap, uint64_t *msg_off,
 				      uint32_t *msg_rec, uint8_t *out, void *d_out, size_t out_cap, lamd_filter_reply_summary *summary);
 
+/* ---- receiving channel_update batches against a store image on the device: the receive path of gossmap_manage_channel_update() /
+ * process_channel_update() (gossipd/gossmap_manage.c:878-1120) for a drained queue of raw messages.  The digest holds what that path asks
+ * the gossmap -- every channel by scid and the timestamp in force per direction --, the directory the two node ids of every channel and the
+ * image itself.  The call looks the channels up, finds the signers, runs ONE signature batch and applies "newer wins, first among equals"
+ * in ARRIVAL ORDER; it returns a verdict per message and the exact bytes and edits gossip_store_add / _del / _set_timestamp
+ * (gossipd/gossip_store.c:49-78, 622-670) would make.  It changes neither the image nor the digest nor the directory: apply the plan,
+ * then build them again.  The digest and the directory must come from this context and from the same image (LAMD_ERR_ARG otherwise).
+ * Message i is msgs + off[i] .. off[i + 1]; source_peers33 + i * peer_stride is the id of the peer it came from (peer_stride 0: one peer for
+ * all; NULL: no message has a source; an id that is no valid key -- 33 zero bytes -- verifies nothing, so it stands for "no source").
+ * STATUS per message: the first that applies, in the reference's order.
+ *   -1  malformed: shorter than 138 bytes, longer than 65535, type not 258, or signature r or s >= n (wire/fromwire.c:196-198).  Bytes behind
+ *       the 138 are legal and are signed.
+ *    1  wrong chain (:1048-1051)
+ *    2  unreasonable timestamp: ts > now + 86400 or ts < now - prune_interval, in unsigned 64-bit arithmetic (:997-1008; prune_interval 0:
+ *       1209600)
+ *    3  held: the scid is in held_scid (ascending), the caller's pending and too-early announcements (:1060-1097).  The caller queues it.
+ *    4  private: the scid is neither a digest entry nor a bare channel, a source peer is given, and the signature verifies under the PEER's
+ *       id (:1101-1110)
+ *    5  unknown channel (:900-917).  The txout-failure set stays with the caller.
+ *    6  bad signature under node_id_1 / node_id_2 of the channel, by channel_flags & 1 (:919-926).  An id that is no valid key, and an
+ *       announcement cut off in front of its ids, fail here.
+ *    7  DONT_FORWARD: message_flags & 2 (:929-932)
+ *    8  stale: ts < the timestamp in force of its slot (channel, direction)       (:935-945)
+ *    9  duplicate: ts == the timestamp in force
+ *    0  accepted
+ *   The timestamp in force of a slot starts as the digest's ts if the slot's record exists, else as "none" (anything that got this far is
+ *   accepted), and then becomes the timestamp of each accepted message in turn.  DELIBERATE: the reference compares with the stored record's
+ *   HEADER timestamp (gossip_store_get_timestamp), the digest holds the SIGNED one; they are equal in every store gossipd or
+ *   lamd_gossip_store_repair_latest wrote.
+ * FLAGS per message (0 unless stated):
+ *   bit 0  SUPERSEDED   accepted, and a later message of the batch was accepted for the same slot: its record is added, then deleted
+ *   bit 1  FIRST        accepted, and the first accepted message, in arrival order over BOTH directions, of a channel whose two slots were
+ *                       both empty: it re-stamps the announcement (:946-951)
+ *   bit 2  DYING        accepted, and the channel's announcement record carries 0x0800 (:957-962)
+ *   bit 3  PEER_UPDATE  accepted and the node of the OTHER direction is our_id33 (:968-978); always set for status 4
+ * chan[i]: the directory's channel number -- the digest's entries, then the bare channels --, UINT32_MAX where the channel is unknown or the
+ *   status is below 4.
+ * THE PLAN
+ *   add_msg[j], add_off[j], j < adds: one store record per accepted message, in arrival order: message add_msg[j]'s record starts at byte
+ *     add_off[j] of the output and is 12 bytes longer than the message: be16 flags = 0x2000 | 0x0800 if DYING | 0x8000 if SUPERSEDED, be16
+ *     len, be32 crc32c seeded with ts, be32 ts, the message -- what the file holds behind its old end after the reference has processed the batch.
+ *   del_rec[k], k < deletions: the image records those slots held before, ascending: set their DELETED bit.
+ *   set_rec / set_ts / set_crc [k], k < retimestamps: for every FIRST, in arrival order: the announcement record, its new header timestamp
+ *     and its recomputed crc.
+ * SIZES  as lamd_short_channel_ids_reply_batch: add_cap must hold the adds, edit_cap the deletions and the re-stamps (each list by itself),
+ *   out_cap the bytes (when out or d_out is given).  One too small: LAMD_ERR_ARG with summary, status, flags and chan filled in and nothing
+ *   written to the plan's arrays, out or d_out.  All caps 0: the verdicts and the sizes alone.  The bytes go to out (host), d_out (device, any
+ *   alignment), or neither.
+ * Device work, on the context's stream: k_rx_classify (one lane per message: byte loads at any alignment, statuses -1 .. 3, two bisections,
+ * the 33-byte signer gathered from the image through the directory, the row's span; rows compacted with one atomic per wave), ONE signature
+ * batch over the spans (the audit's form; the spans behind the last row are empty), k_rx_settle, a stable rocPRIM radix sort of the
+ * candidates by slot = 2 * chan + direction, an inclusive max-scan over (slot << 33) | (ts + 1) -- slots ascend, so the row in front tells a row
+ * its slot's maximum so far, whatever the number of messages aimed at one slot --, k_rx_resolve (accepted iff ts + 1 > max(seed, that);
+ * SUPERSEDED from the slot's last row, FIRST from the other slot's head, both by bisection), a sort of the deleted records, three exclusive
+ * scans in arrival order, k_rx_plan, and behind the first wait k_rx_encode (headers, CRC-32C) and k_rx_copy (one aligned 32-bit word of the
+ * output per lane).  The host waits once for the verdicts and sizes and once for the lists and bytes.  Limits: n below 2^31, fewer than 2^30
+ * channels, off non-decreasing. */
+typedef struct {
+	uint64_t by_status[11];     /* messages: [0] .. [9] statuses 0 .. 9, [10] malformed */
+	uint64_t accepted, superseded;
+	uint64_t adds, bytes;       /* what add_cap and out_cap must hold */
+	uint64_t deletions, retimestamps;   /* what edit_cap must hold, each */
+	double stage_ms[5];         /* with lamd_set_timing: classify, signatures, resolve, plan, encode */
+	uint64_t signature_rows;    /* the rows of the signature batch */
+} lamd_update_receive_summary;
+int lamd_channel_update_receive_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const lamd_store_directory *directory,
+				      const uint8_t *chain_hash32, uint64_t now, uint32_t prune_interval, const uint8_t *our_id33, size_t n,
+				      const uint8_t *msgs, const uint64_t *off, const uint8_t *source_peers33, size_t peer_stride, size_t n_held,
+				      const uint64_t *held_scid, int8_t *status, uint8_t *flags, uint32_t *chan, size_t add_cap, uint32_t *add_msg,
+				      uint64_t *add_off, uint8_t *out, void *d_out, size_t out_cap, size_t edit_cap, uint32_t *del_rec,
+				      uint32_t *set_rec, uint32_t *set_ts, uint32_t *set_crc, lamd_update_receive_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

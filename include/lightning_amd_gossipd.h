@@ -26,7 +26,8 @@
  * seeker's comparison of peers' reply_channel_range with the store is lamd_channel_range_compare_batch, include/lightning_amd.h; the
  * query_short_channel_ids responder is lamd_short_channel_ids_reply_batch and a peer's gossip_timestamp_filter is answered by
  * lamd_timestamp_filter_reply_batch, both from the same image; the per-peer state of a stream -- gossip_rcvd_filter, the 60-second
- * timer, dev_suppress_gossip -- stays with the caller) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
+ * timer, dev_suppress_gossip -- stays with the caller; the channel_update half of step 1 - 3 against such an image, look-ups and replay on
+ * the device, is lamd_channel_update_receive_batch) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
  * append to / delete from / re-flag the store) and it does the I/O.
  *
  * Everything observable is reported through the event callback, in the order the reference would produce it; texts

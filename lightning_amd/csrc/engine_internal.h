@@ -195,14 +195,16 @@ struct lamd_ctx {
   // block sums, node table, and the output image; digest build: its tables and the sort's workspace; range replies: plan arrays, the messages;
   // range comparison: the peers' messages, classes, lists, the sorts' workspace, and the queries it writes; directory build: candidates, keys,
   // permutations, the sorts' workspace; short_channel_ids replies: the queries, per-occurrence and per-node arrays, offsets, and the messages.
+  // channel_update reception: the batch, its per-message, per-row and per-slot arrays, the plan, and the added records.
   // t_audit / t_rep: the stage boundaries of an audit and of a repair's own stages; t_dig: those of a digest or directory build, a range reply, a
-  // comparison, a short_channel_ids reply, a stream index build or a timestamp filter reply
+  // comparison, a short_channel_ids reply, a stream index build or a timestamp filter reply; t_rx: those of a channel_update reception
   struct store_ws {
-    devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out, dir, sq, sq_out, ts, ts_msg, ts_out;
+    devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out, dir, sq, sq_out, ts, ts_msg, ts_out, rx, rx_out;
     stage_timer<6> t_audit;
     stage_timer<4> t_rep;
     stage_timer<6> t_dig;
-    void destroy_events() { t_audit.destroy(); t_rep.destroy(); t_dig.destroy(); }
+    stage_timer<7> t_rx;
+    void destroy_events() { t_audit.destroy(); t_rep.destroy(); t_dig.destroy(); t_rx.destroy(); }
   } store;
   // text front ends (lamd_frontends.hip: lamd_bolt11_check_batch, lamd_checkmessage_batch, lamd_bolt12_check_text_batch): the per-row columns; events in
   // front of the front-end kernel, behind it, behind the merge; what they measured last: front end, curve work + merge

@@ -1,5 +1,6 @@
 // liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies, the comparison of peers' replies,
-// the directory of an image and the answers to query_short_channel_ids, the stream index of an image and the answers to gossip_timestamp_filter
+// the directory of an image and the answers to query_short_channel_ids, the stream index of an image and the answers to gossip_timestamp_filter,
+// the reception of channel_update batches against an image
 #include "engine_internal.h"
 #include "store_audit.h"
 #include "store_repair.h"
@@ -8,18 +9,16 @@
 #include "store_compare.h"
 #include "store_query.h"
 #include "store_stream.h"
+#include "store_receive.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <memory>
 
 // ---- gossip_store audit (lamd_gossip_store_audit; per-record logic in store_audit.h).  One lane per record throughout.
-// k_store_crc: the block builds the slicing tables in LDS (thread t computes entry t of table 0 from the bitwise definition; every further
-// table reads table 0 only), then each lane checksums its record -- bytes until the pointer is 4-aligned, 32-bit loads, tail bytes -- and
-// classifies it.  A lane's cost is its record's length: gossip records are 130-450 bytes, the 65 535-byte maximum is correct, not fast.
+// The slicing tables of the CRC-32C in LDS, built by a block of 256 threads: thread t computes entry t of table 0 from the bitwise definition,
+// every further table reads table 0 only.  Ends behind a barrier: every thread may read T.
 template <int WAYS>
-__global__ void __launch_bounds__(256) k_store_crc(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
-                                                   int8_t *__restrict__ pre) {
-  __shared__ u32 T[WAYS * 256];
+__device__ __forceinline__ void block_crc_tables(u32 *T) {
   const u32 t = threadIdx.x;
   u32 v = store_crc_t0(t);
   T[t] = v;
@@ -29,7 +28,16 @@ __global__ void __launch_bounds__(256) k_store_crc(u32 n, const u8 *__restrict__
     T[256 * k + t] = v;
   }
   __syncthreads();
-  const u32 i = blockIdx.x * 256 + t;
+}
+// k_store_crc: the block builds the slicing tables in LDS (block_crc_tables), then each lane checksums its record -- bytes until the pointer
+// is 4-aligned, 32-bit loads, tail bytes -- and classifies it.  A lane's cost is its record's length: gossip records are 130-450 bytes, the
+// 65 535-byte maximum is correct, not fast.
+template <int WAYS>
+__global__ void __launch_bounds__(256) k_store_crc(u32 n, const u8 *__restrict__ store, size_t store_len, const u64 *__restrict__ rec_off,
+                                                   int8_t *__restrict__ pre) {
+  __shared__ u32 T[WAYS * 256];
+  block_crc_tables<WAYS>(T);
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) pre[i] = (int8_t)store_precheck_one<WAYS>(T, store, store_len, rec_off[i]);
 }
 // keys / vals: (1 << bits) + 1 slots, preset to all-ones bytes (STORE_EMPTY_KEY / STORE_NONE)
@@ -250,16 +258,8 @@ __global__ void __launch_bounds__(256) k_digest_entries(u32 n, const u8 *__restr
                                                         const u32 *__restrict__ slot, const u32 *__restrict__ ann, const u32 *__restrict__ cnt,
                                                         u32 *__restrict__ ts, u32 *__restrict__ csum, u32 *__restrict__ rec) {
   __shared__ u32 T[4 * 256];
-  const u32 t = threadIdx.x;
-  u32 v = store_crc_t0(t);
-  T[t] = v;
-  __syncthreads();
-  for (int k = 1; k < 4; k++) {
-    v = (v >> 8) ^ T[v & 0xff];
-    T[256 * k + t] = v;
-  }
-  __syncthreads();
-  const u32 j = blockIdx.x * 256 + t, count = cnt[DIGEST_CNT_ENTRIES] < n ? cnt[DIGEST_CNT_ENTRIES] : n;
+  block_crc_tables<4>(T);
+  const u32 j = blockIdx.x * 256 + threadIdx.x, count = cnt[DIGEST_CNT_ENTRIES] < n ? cnt[DIGEST_CNT_ENTRIES] : n;
   if (j >= count) return;
   const u32 a = ann[j];
   if (a >= n) return;   // (never: the first `count` pairs are real)
@@ -1962,6 +1962,247 @@ extern "C" int lamd_timestamp_filter_reply_batch(lamd_ctx *ctx, const lamd_store
       STCHK(hipEventElapsedTime(&ms, ctx->store.t_dig.ev[4], ctx->store.t_dig.ev[5]));
       summary->stage_ms[3] = ms;
     }
+  }
+  return LAMD_OK;
+}
+
+// ---- channel_update reception (lamd_channel_update_receive_batch; per-message, per-row and per-word logic in store_receive.h).  One lane per
+// message, per sorted position or per output word; each stage reads what the one before it wrote, so each is a launch of its own.
+// cnt: RX_CNT_* words, all 0.
+enum { RX_CNT_ROWS = 0, RX_CNT_DELS = 1, RX_CNTS = 4 };
+// k_rx_classify: statuses -1 .. 3, the two bisections, the signer; the PENDING messages get consecutive signature rows with one atomic per
+// wave (in any order: row_msg / row_of tie a row to its message).  rowbase: the identity, one row per span.  start / len: preset to 0 -- the
+// rows behind the last real one are empty spans: nothing is read through them, their rows of the signature batch are all-zero and fail.
+__global__ void __launch_bounds__(256) k_rx_classify(store_rx_view v, store_rx_params p, store_rx_batch b, int8_t *__restrict__ status, u32 *__restrict__ chan,
+                                                     u32 *__restrict__ ts, u8 *__restrict__ aux, u32 *__restrict__ row_of, u64 *__restrict__ start,
+                                                     u64 *__restrict__ len, u8 *__restrict__ ids33, u32 *__restrict__ row_msg, u64 *__restrict__ rowbase, u32 *cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  store_rx_msg r;
+  r.status = STORE_RX_MALFORMED;
+  if (i < b.n) {
+    r = store_rx_classify(v, p, b, i);
+    status[i] = (int8_t)r.status;
+    chan[i] = r.chan;
+    ts[i] = r.ts;
+    aux[i] = (u8)(r.dir | (r.dont_forward << 1));
+    rowbase[i] = i;
+    if (i == b.n - 1) rowbase[b.n] = b.n;
+  }
+  const bool pending = i < b.n && r.status == STORE_RX_PENDING;
+  const u32 row = wave_alloc(&cnt[RX_CNT_ROWS], pending);
+  if (i < b.n) row_of[i] = pending ? row : STORE_NONE;
+  if (pending && row < b.n) store_rx_row(v, b, r, i, row, start, len, ids33, row_msg);
+}
+__global__ void __launch_bounds__(256) k_rx_settle(u32 n, int8_t *__restrict__ status, u8 *__restrict__ flags, const u32 *__restrict__ chan,
+                                                   const u8 *__restrict__ aux, const u32 *__restrict__ row_of, const int8_t *__restrict__ sigv,
+                                                   u64 *__restrict__ key, u32 *__restrict__ val) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  key[i] = store_rx_settle(status, flags, chan, aux, row_of, sigv, i);
+  val[i] = i;
+}
+__global__ void __launch_bounds__(256) k_rx_items(u32 n, const u64 *__restrict__ key, const u32 *__restrict__ val, const u32 *__restrict__ ts,
+                                                  u64 *__restrict__ item) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  if (p < n) item[p] = store_rx_item(key, val, ts, p);
+}
+__global__ void __launch_bounds__(256) k_rx_resolve(store_rx_view v, store_rx_params pr, store_rx_batch b, store_rx_sorted s, const u32 *__restrict__ ts,
+                                                    int8_t *status, u8 *flags, store_rx_marks k, u32 *cnt) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  const bool deletes = p < s.n && store_rx_resolve(v, pr, b, s, ts, p, status, flags, k);
+  wave_count(&cnt[RX_CNT_DELS], deletes);
+}
+// k_rx_plan: where each accepted message's record goes, and the re-stamped announcements with their checksums.  The CRC tables as in k_store_crc.
+__global__ void __launch_bounds__(256) k_rx_plan(u32 n, store_rx_view v, const int8_t *__restrict__ status, const u8 *__restrict__ flags,
+                                                 const u32 *__restrict__ chan, const u32 *__restrict__ ts, const u64 *__restrict__ apos,
+                                                 const u64 *__restrict__ abyte, const u64 *__restrict__ spos, store_rx_plan_out o) {
+  __shared__ u32 T[4 * 256];
+  block_crc_tables<4>(T);
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_rx_plan<4>(T, v, status, flags, chan, ts, apos, abyte, spos, o, i);
+}
+// k_rx_encode: one lane per added record writes its 12-byte header; k_rx_copy: one aligned 32-bit word of the output per lane
+__global__ void __launch_bounds__(256) k_rx_encode(u32 adds, store_rx_batch b, const u32 *__restrict__ add_msg, const u8 *__restrict__ flags,
+                                                   const u32 *__restrict__ ts, u8 *__restrict__ hdr) {
+  __shared__ u32 T[4 * 256];
+  block_crc_tables<4>(T);
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j < adds) store_rx_header<4>(T, b, flags, ts, add_msg[j], hdr + STORE_HDR * (size_t)j);
+}
+__global__ void __launch_bounds__(256) k_rx_copy(u64 words, store_rx_out o, u8 *__restrict__ out, u64 total) {
+  const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (k < words) store_rx_word(o, out, total, (u32)((uintptr_t)out & 3), k);
+}
+
+// the workspace of one call, carved out of store.rx: with base == nullptr the same walk gives its size
+struct rx_ws {
+  u64 *off, *start, *len, *rowbase, *key, *skey, *item, *run, *apos, *abyte, *spos, *add_off, *held;
+  u32 *chan, *ts, *row_of, *row_msg, *val, *sval, *acnt, *abytes, *scnt, *del_key, *del_sorted, *add_msg, *set_rec, *set_ts, *set_crc, *cnt;
+  int8_t *status, *sigv;
+  u8 *flags, *aux, *ids33, *hdr, *msgs, *peers, *tmp;
+  size_t bytes;
+  rx_ws(u8 *base, size_t n, size_t n_held, size_t msg_bytes, size_t peer_bytes, size_t tmp_bytes) {
+    size_t at = 0;
+    auto take = [&](auto **p, size_t count) {
+      using T = std::remove_reference_t<decltype(**p)>;
+      *p = base ? (T *)(base + at) : nullptr;
+      at += sizeof(T) * count;
+    };
+    take(&off, n + 1); take(&start, n); take(&len, n); take(&rowbase, n + 1); take(&key, n); take(&skey, n); take(&item, n); take(&run, n);
+    take(&apos, n + 1); take(&abyte, n + 1); take(&spos, n + 1); take(&add_off, n + 1); take(&held, n_held);
+    take(&chan, n); take(&ts, n); take(&row_of, n); take(&row_msg, n); take(&val, n); take(&sval, n);
+    take(&acnt, n + 1); take(&abytes, n + 1); take(&scnt, n + 1);   // (one memset clears the three)
+    take(&del_key, n); take(&del_sorted, n); take(&add_msg, n); take(&set_rec, n); take(&set_ts, n); take(&set_crc, n); take(&cnt, RX_CNTS);
+    take(&status, n); take(&sigv, n); take(&flags, n); take(&aux, n); take(&ids33, 33 * n); take(&hdr, STORE_HDR * n); take(&msgs, msg_bytes + 1);
+    take(&peers, peer_bytes);
+    at = align_up(at, 256);
+    take(&tmp, tmp_bytes);
+    bytes = at + 16;
+  }
+};
+
+extern "C" int lamd_channel_update_receive_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const lamd_store_directory *directory,
+                                                 const uint8_t *chain_hash32, uint64_t now, uint32_t prune_interval, const uint8_t *our_id33, size_t n,
+                                                 const uint8_t *msgs, const uint64_t *off, const uint8_t *source_peers33, size_t peer_stride, size_t n_held,
+                                                 const uint64_t *held_scid, int8_t *status, uint8_t *flags, uint32_t *chan, size_t add_cap, uint32_t *add_msg,
+                                                 uint64_t *add_off, uint8_t *out, void *d_out, size_t out_cap, size_t edit_cap, uint32_t *del_rec,
+                                                 uint32_t *set_rec, uint32_t *set_ts, uint32_t *set_crc, lamd_update_receive_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!digest || !directory || !chain_hash32 || !summary || (n && (!msgs || !off || !status || !flags || !chan)) || (add_cap && (!add_msg || !add_off)) ||
+      (edit_cap && (!del_rec || !set_rec || !set_ts || !set_crc)) || (n_held && !held_scid) || (source_peers33 && peer_stride && peer_stride < 33) ||
+      n >= (size_t)STORE_NONE / 2 || n_held >= (size_t)STORE_NONE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  // the digest and the directory of ONE image, built by this context (as lamd_gossip_store_directory_build checks its digest)
+  if (digest->ctx != ctx || directory->ctx != ctx || directory->n != digest->cap || directory->count != digest->count || directory->nbare != digest->nbare) {
+    ctx->err = "channel_update receive: the digest and the directory do not belong to this context and to one image";
+    return LAMD_ERR_ARG;
+  }
+  if ((u64)directory->count + directory->nbare >= STORE_RX_MAX_CHANNELS) { ctx->err = "channel_update receive: too many channels"; return LAMD_ERR_ARG; }
+  *summary = lamd_update_receive_summary();
+  if (n == 0) return LAMD_OK;
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) { ctx->err = "channel_update receive: decreasing message offsets"; return LAMD_ERR_ARG; }
+  for (size_t k = 1; k < n_held; k++)
+    if (held_scid[k] <= held_scid[k - 1]) { ctx->err = "channel_update receive: held_scid is not ascending"; return LAMD_ERR_ARG; }
+  const size_t msg_bytes = (size_t)(off[n] - off[0]), peer_bytes = source_peers33 ? (n - 1) * peer_stride + 33 : 0;
+  std::vector<u64> rel(n + 1);   // a queued copy reads it: STCHK drains the stream
+  for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+  store_rx_params pr;
+  pr.now = now;
+  pr.prune = prune_interval ? prune_interval : 1209600;
+  pr.have_our = our_id33 != nullptr;
+  memcpy(pr.chain, chain_hash32, 32);
+  memset(pr.our_id, 0, 33);
+  if (our_id33) memcpy(pr.our_id, our_id33, 33);
+  lamd_ctx *L = ctx;
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  size_t tmp_bytes = 0, need = 0;
+  STCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 32, st));
+  STCHK(rocprim::radix_sort_keys(nullptr, need, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 32, st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  STCHK(rocprim::inclusive_scan(nullptr, need, (const u64 *)nullptr, (u64 *)nullptr, n, rocprim::maximum<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  STCHK(rocprim::exclusive_scan(nullptr, need, (const u32 *)nullptr, (u64 *)nullptr, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.rx, rx_ws(nullptr, n, n_held, msg_bytes, peer_bytes, tmp_bytes).bytes)) != LAMD_OK) return rc;
+  const rx_ws w(ctx->store.rx.as<u8>(), n, n_held, msg_bytes, peer_bytes, tmp_bytes);
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_rx.create());
+  STCHK(hipMemcpyAsync(w.off, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+  if (msg_bytes) STCHK(hipMemcpyAsync(w.msgs, msgs + off[0], msg_bytes, hipMemcpyHostToDevice, st));
+  if (peer_bytes) STCHK(hipMemcpyAsync(w.peers, source_peers33, peer_bytes, hipMemcpyHostToDevice, st));
+  if (n_held) STCHK(hipMemcpyAsync(w.held, held_scid, 8 * n_held, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(w.start, 0, 16 * n, st));                  // start, len
+  STCHK(hipMemsetAsync(w.acnt, 0, 12 * (n + 1), st));             // acnt, abytes, scnt
+  STCHK(hipMemsetAsync(w.del_key, 0xFF, 4 * n, st));
+  STCHK(hipMemsetAsync(w.cnt, 0, 4 * RX_CNTS, st));
+  STCHK(hipMemsetAsync(w.flags, 0, n, st));
+  const store_rx_view v{directory->img, directory->img_len, directory->rec_off, (u32)directory->n, directory->scid, (u32)directory->count, (u32)directory->nbare,
+                        directory->ent_rec, directory->bare_rec, digest->ts};
+  const store_rx_batch b{w.msgs, w.off, (u32)n, peer_bytes ? w.peers : nullptr, (u64)peer_stride, w.held, (u32)n_held};
+  const dim3 grid(blocks_for(n)), block(256);
+  if (timed) STCHK(ctx->store.t_rx.record(0, st));
+  hipLaunchKernelGGL(k_rx_classify, grid, block, 0, st, v, pr, b, w.status, w.chan, w.ts, w.aux, w.row_of, w.start, w.len, w.ids33, w.row_msg, w.rowbase, w.cnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(1, st));
+  // ONE signature batch over n spans: the real rows in front, empty spans behind them (the host does not wait for their number)
+  if ((rc = gossip_device(ctx, n, w.msgs, w.start, w.ids33, w.rowbase, n, w.sigv, w.len)) != LAMD_OK) return drain_fail(ctx, L, rc);
+  if (timed) STCHK(ctx->store.t_rx.record(2, st));
+  hipLaunchKernelGGL(k_rx_settle, grid, block, 0, st, (u32)n, w.status, w.flags, (const u32 *)w.chan, (const u8 *)w.aux, (const u32 *)w.row_of,
+                     (const int8_t *)w.sigv, w.key, w.val);
+  // stable: arrival order inside a slot; the slots need 31 bits, the pads (all ones) end behind them
+  STCHK(rocprim::radix_sort_pairs(w.tmp, tmp_bytes, (const u64 *)w.key, w.skey, (const u32 *)w.val, w.sval, n, 0, 32, st));
+  hipLaunchKernelGGL(k_rx_items, grid, block, 0, st, (u32)n, (const u64 *)w.skey, (const u32 *)w.sval, (const u32 *)w.ts, w.item);
+  STCHK(rocprim::inclusive_scan(w.tmp, tmp_bytes, (const u64 *)w.item, w.run, n, rocprim::maximum<u64>(), st));
+  hipLaunchKernelGGL(k_rx_resolve, grid, block, 0, st, v, pr, b, store_rx_sorted{w.skey, w.sval, w.run, (u32)n}, (const u32 *)w.ts, w.status, w.flags,
+                     store_rx_marks{w.acnt, w.abytes, w.scnt, w.del_key}, w.cnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(3, st));
+  STCHK(rocprim::radix_sort_keys(w.tmp, tmp_bytes, (const u32 *)w.del_key, w.del_sorted, n, 0, 32, st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.acnt, w.apos, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.abytes, w.abyte, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.scnt, w.spos, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  hipLaunchKernelGGL(k_rx_plan, grid, block, 0, st, (u32)n, v, (const int8_t *)w.status, (const u8 *)w.flags, (const u32 *)w.chan, (const u32 *)w.ts,
+                     (const u64 *)w.apos, (const u64 *)w.abyte, (const u64 *)w.spos, store_rx_plan_out{(u64)n, (u64)n, w.add_msg, w.add_off, w.set_rec, w.set_ts, w.set_crc});
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(4, st));
+  u64 totals[3] = {0, 0, 0};
+  u32 cnt[RX_CNTS] = {};
+  STCHK(hipMemcpyAsync(status, w.status, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(flags, w.flags, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(chan, w.chan, 4 * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[0], w.apos + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[1], w.abyte + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[2], w.spos + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(cnt, w.cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: verdicts and sizes
+  if (timed) STCHK(ctx->store.t_rx.read(4, summary->stage_ms));
+  for (size_t i = 0; i < n; i++) {
+    summary->by_status[status[i] < 0 ? 10 : status[i] <= 9 ? status[i] : 10]++;
+    summary->superseded += (flags[i] & STORE_RX_SUPERSEDED) != 0;
+  }
+  const u64 adds = totals[0], total = totals[1], sets = totals[2], dels = cnt[RX_CNT_DELS];
+  summary->accepted = summary->adds = adds;
+  summary->bytes = total;
+  summary->deletions = dels;
+  summary->retimestamps = sets;
+  summary->signature_rows = cnt[RX_CNT_ROWS];
+  const bool want_out = out || d_out;
+  if (adds > add_cap) { ctx->err = "channel_update receive: add_msg / add_off too small"; return LAMD_ERR_ARG; }
+  if (want_out && total > out_cap) { ctx->err = "channel_update receive: output buffer too small"; return LAMD_ERR_ARG; }
+  if (dels > edit_cap || sets > edit_cap) { ctx->err = "channel_update receive: the edit lists are too small"; return LAMD_ERR_ARG; }
+  if (adds) {
+    STCHK(hipMemcpyAsync(add_msg, w.add_msg, 4 * adds, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(add_off, w.add_off, 8 * adds, hipMemcpyDeviceToHost, st));
+  }
+  if (dels) STCHK(hipMemcpyAsync(del_rec, w.del_sorted, 4 * dels, hipMemcpyDeviceToHost, st));
+  if (sets) {
+    STCHK(hipMemcpyAsync(set_rec, w.set_rec, 4 * sets, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(set_ts, w.set_ts, 4 * sets, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(set_crc, w.set_crc, 4 * sets, hipMemcpyDeviceToHost, st));
+  }
+  const bool encode = want_out && adds;
+  if (encode) {
+    if (!d_out && (rc = ensure(ctx, &ctx->store.rx_out, total + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+    u8 *d_bytes = d_out ? (u8 *)d_out : ctx->store.rx_out.as<u8>();
+    const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+    if (timed) STCHK(ctx->store.t_rx.record(5, st));
+    hipLaunchKernelGGL(k_rx_encode, dim3(blocks_for(adds)), block, 0, st, (u32)adds, b, (const u32 *)w.add_msg, (const u8 *)w.flags, (const u32 *)w.ts, w.hdr);
+    hipLaunchKernelGGL(k_rx_copy, dim3((unsigned)((words + 255) / 256)), block, 0, st, words,
+                       store_rx_out{w.add_off, w.add_msg, (u32)adds, w.hdr, w.msgs, w.off}, d_bytes, total);
+    STCHK(hipGetLastError());
+    if (timed) STCHK(ctx->store.t_rx.record(6, st));
+    if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  }
+  STCHK(hipStreamSynchronize(st));   // the second wait: the lists and the bytes
+  if (timed && encode) {
+    float ms = 0;
+    STCHK(hipEventElapsedTime(&ms, ctx->store.t_rx.ev[5], ctx->store.t_rx.ev[6]));
+    summary->stage_ms[4] = ms;
   }
   return LAMD_OK;
 }

@@ -79,6 +79,24 @@ def gossip_store_frame(blob):
     return off[:n.value], _store_summary(s)
 
 
+def apply_update_plan(blob, rec_off, plan):
+    """the plan of Engine.channel_update_receive applied to the image it was made for, in numpy: the DELETED bit of every del_rec set, the
+    headers of the set_rec announcements re-stamped (timestamp and crc), the added records appended behind the old end.
+    -> (image bytes, rec_off uint64 extended by the added records): audit it, or build digest, directory and stream index again"""
+    img, n_bytes, _ = _store_blob(blob)
+    if plan["records"] is None:
+        raise ValueError("the plan holds no record bytes (host_out=False)")
+    off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    out = np.concatenate([img[:n_bytes], np.frombuffer(plan["records"], dtype=np.uint8)])
+    out[off[np.asarray(plan["del_rec"], dtype=np.int64)].astype(np.int64)] |= 0x80
+    at = off[np.asarray(plan["set_rec"], dtype=np.int64)].astype(np.int64)
+    for k, word in ((4, plan["set_crc"]), (8, plan["set_ts"])):
+        be = np.asarray(word, dtype=">u4").view(np.uint8).reshape(-1, 4)
+        for x in range(4):
+            out[at + k + x] = be[:, x]
+    return out.tobytes(), np.concatenate([off, np.uint64(n_bytes) + np.asarray(plan["add_off"], dtype=np.uint64)])
+
+
 class StoreDigest:
     """lamd_store_digest: the channel digest Engine.gossip_store_digest built, resident on the device.  close() it before its Engine."""
 
@@ -772,6 +790,77 @@ class Engine:
         res = (status[:n], cursor_out[:n], done[:n], [[raw[int(msg_off[j]):int(msg_off[j + 1])] for j in sp] for sp in spans])
         if return_records:
             res += ([[int(msg_rec[j]) for j in sp] for sp in spans],)
+        if return_summary:
+            res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
+
+    def channel_update_receive(self, digest, directory, msgs, chain_hash=None, now=0, prune_interval=0, our_id=None, peers=None, held=(),
+                               d_out=None, host_out=True, return_summary=False):
+        """lamd_channel_update_receive_batch: a drained queue of raw channel_update messages received against the image a StoreDigest and a
+        StoreDirectory were built from (both by this Engine): look-ups, signers, ONE signature batch, "newer wins, first among equals" in arrival
+        order.  msgs: a list of messages, or (blob uint8, off uint64 [n + 1]): message i = blob[off[i]:off[i + 1]].  chain_hash: the 32 bytes of our chain (default: the one given to gossip_store_directory); now: the clock in seconds;
+        prune_interval: 0 = 1209600; our_id: our 33-byte node id or None; peers: None, one 33-byte id for all messages, or one per message (None
+        there: no source); held: the scids of the caller's pending and too-early announcements; d_out: a torch uint8 CUDA tensor the added
+        records are written to (at its data pointer, any alignment) instead of, or with host_out besides, the host.
+        -> (status int8 [msgs] (0 accepted, -1 malformed, 1 wrong chain, 2 timestamp, 3 held, 4 private, 5 unknown channel, 6 bad signature,
+        7 DONT_FORWARD, 8 stale, 9 duplicate), flags uint8 [msgs] (1 SUPERSEDED, 2 FIRST, 4 DYING, 8 PEER_UPDATE), chan uint32 [msgs]
+        (0xFFFFFFFF: none), plan): plan = dict(add_msg uint32 [adds], add_off uint64 [adds], records bytes or None (without host_out), del_rec
+        uint32 ascending, set_rec / set_ts / set_crc uint32 [re-stamps]) -- apply_update_plan() applies it to the image"""
+        if chain_hash is None:
+            chain_hash = directory.chain_hash
+        if chain_hash is None:
+            raise ValueError("a chain_hash is needed: here or at gossip_store_directory")
+        chain = np.frombuffer(bytes(chain_hash), dtype=np.uint8)
+        if chain.size != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        if isinstance(msgs, tuple):                       # (blob uint8, off uint64 [n + 1]): a drained queue in one buffer
+            blob, off = np.ascontiguousarray(msgs[0], dtype=np.uint8), np.ascontiguousarray(msgs[1], dtype=np.uint64)
+            n = off.size - 1
+            if n < 0 or (n and int(off[n]) > blob.size):
+                raise ValueError("the offsets do not fit the blob")
+        else:
+            n = len(msgs)
+            off = np.zeros(n + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\x00", dtype=np.uint8)
+        ours = None
+        if our_id is not None:
+            ours = np.frombuffer(bytes(our_id), dtype=np.uint8)
+            if ours.size != 33:
+                raise ValueError("a node id has 33 bytes")
+        pid, stride = None, 0
+        if peers is not None and n:
+            if isinstance(peers, (bytes, bytearray)):
+                pid = np.frombuffer(bytes(peers), dtype=np.uint8)
+            else:
+                if len(peers) != n:
+                    raise ValueError("one peer per message")
+                pid, stride = np.frombuffer(b"".join(bytes(33) if p is None else bytes(p) for p in peers), dtype=np.uint8), 33
+            if pid.size != (33 if stride == 0 else 33 * n):
+                raise ValueError("a node id has 33 bytes")
+        hs = np.array(sorted(set(int(s) for s in held)) + [0], dtype=np.uint64)
+        status, flags, chan = np.zeros(max(1, n), dtype=np.int8), np.zeros(max(1, n), dtype=np.uint8), np.zeros(max(1, n), dtype=np.uint32)
+        # no plan is longer than the batch: one call, no sizing pass (it would run the signature batch twice)
+        cap, nbytes = max(1, n), max(1, int(off[n] - off[0]) + 12 * n)
+        add_msg, add_off = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint64)
+        del_rec, set_rec, set_ts, set_crc = (np.zeros(cap, dtype=np.uint32) for _ in range(4))
+        out = np.zeros(nbytes, dtype=np.uint8) if host_out else None
+        d_ptr = None
+        if d_out is not None:
+            if d_out.numel() < nbytes:
+                raise ValueError("d_out must hold the messages and 12 bytes each")
+            self._after_torch()
+            d_ptr = d_out.data_ptr()
+        s = _ffi.LamdUpdateReceiveSummary()
+        self._chk(self._lib.lamd_channel_update_receive_batch(
+            self._ctx, digest._h, directory._h, chain.ctypes.data, int(now), int(prune_interval), None if ours is None else ours.ctypes.data, n,
+            blob.ctypes.data, off.ctypes.data, None if pid is None else pid.ctypes.data, stride, hs.size - 1, hs.ctypes.data if hs.size > 1 else None,
+            status.ctypes.data, flags.ctypes.data, chan.ctypes.data, cap, add_msg.ctypes.data, add_off.ctypes.data,
+            None if out is None else out.ctypes.data, d_ptr, nbytes, cap, del_rec.ctypes.data, set_rec.ctypes.data, set_ts.ctypes.data, set_crc.ctypes.data,
+            ctypes.byref(s)))
+        plan = dict(add_msg=add_msg[:s.adds], add_off=add_off[:s.adds], records=None if out is None else out[:s.bytes].tobytes(), del_rec=del_rec[:s.deletions],
+                    set_rec=set_rec[:s.retimestamps], set_ts=set_ts[:s.retimestamps], set_crc=set_crc[:s.retimestamps])
+        res = (status[:n], flags[:n], chan[:n], plan)
         if return_summary:
             res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
         return res
