@@ -382,6 +382,16 @@ int lamd_sigcheck_gossip_spans_device(lamd_ctx *ctx, size_t n, const void *d_msg
  * Verdicts of different records are independent except for the signer look-up: an update is judged against the node ids of its
  * announcement whatever that announcement's own verdict.  Live or dead is decided by the FLAGS ALONE: gossipd itself marks what a
  * delete_chan tombstone (4103) removes as DELETED (gossip_store.c:622-638), so tombstones are checksummed and counted, never applied.
+ * THIS DIFFERS FROM THE REFERENCE'S LOADERS, which do apply one: common/gossmap.c removes the tombstone's channel
+ * (:900-901, remove_channel_by_deletemsg :612-626) and so does pyln's Gossmap.  On a store gossipd wrote the result is the same, because
+ * remove_channel writes the tombstone AND flags the announcement, its amount record and its updates DELETED (gossmap_manage.c:318-328).
+ * On a store where a valid tombstone stands behind records that are not flagged, it is not: gossmap.c drops the channel (and a node that
+ * has no other), this library keeps both in digest, bare list and directory.  The one natural case is among the reference's own
+ * fixtures: the last record of contrib/pyln-client/tests/data/gossip_store-part2.xz (2021) is a tombstone for 686386x1093x1 whose
+ * announcement is not flagged.  As shipped it also fails its CRC: pyln checks none and drops the channel; gossmap.c checks
+ * (csum_matches, :870-888) and stops loading in front of it, so the channel survives there; here the record is LAMD_STORE_BAD_CHECKSUM and
+ * the channel stays.  With the CRC corrected gossmap.c would drop the channel and this library still keeps it: tests/test_reference_stores.py
+ * pins that difference, the repairs included: they drop the tombstone's own record and keep the channel it names.
  * Records 4101 / 4106 / 4107 get the checksum only; following store_ended into the new file, dying deadlines, the upgrade of old versions
  * and the legacy 0x4000 push bit of version 15 (ignored) are left to the reference's own load. */
 enum {

@@ -4,10 +4,13 @@
 //  - the scid index: lowest record wins, the key that looks like an empty slot, colliding keys;
 //  - store_walk on truncated, zero-filled and garbage-length files.  Every buffer handed to the walk is a heap block of EXACTLY len bytes,
 //    so a read past the end is an ASan report.
+// With three arguments, IMAGE SIGV OUT, it runs none of those: it audits the store file IMAGE with the signature verdicts handed in and writes
+// offsets, verdicts, signers and the walk's summary to OUT.* for the test to compare with the sequential model (audit_file below).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "store_audit.h"
@@ -56,10 +59,72 @@ static walked walk(const std::vector<u8> &f, size_t len) {
   return w;
 }
 
-int main() {
+static std::vector<u8> read_file(const char *path) {
+  std::vector<u8> out;
+  FILE *f = fopen(path, "rb");
+  if (!f) { printf("cannot read %s\n", path); exit(2); }
+  u8 tmp[4096];
+  for (size_t k; (k = fread(tmp, 1, sizeof tmp, f)) > 0;) out.insert(out.end(), tmp, tmp + k);
+  fclose(f);
+  return out;
+}
+static void write_file(const std::string &path, const void *p, size_t len) {
+  FILE *f = fopen(path.c_str(), "wb");
+  if (!f || fwrite(p, 1, len, f) != len) { printf("cannot write %s\n", path.c_str()); exit(2); }
+  fclose(f);
+}
+
+// IMAGE SIGV OUT: the audit of a store file with the signature verdicts handed in (SIGV: one int8 per record, what the signature batch says
+// of it; read for live records of type 256 / 257 / 258 only).  The walk, both CRC widths, the scid index filled in file order and in reverse,
+// the signer look-up and the merge -> OUT.off (u64 per record), OUT.verdict (int8), OUT.signer (33 bytes per record), OUT.walk (5 x u64:
+// records, live, deleted, end_offset, end_reason).
+static int audit_file(const char *image, const char *sigv_path, const std::string &base, const u32 *T4, const u32 *T8) {
+  const std::vector<u8> file = read_file(image), sigv = read_file(sigv_path);
+  const size_t len = file.size();
+  u8 *buf = (u8 *)malloc(len ? len : 1);   // exactly the file: a read past it is an ASan report
+  if (len) memcpy(buf, file.data(), len);
+  lamd_store_summary s;
+  std::vector<u64> off;
+  std::vector<u32> type;
+  if (!store_walk(buf, len, &s, [&](size_t, u64 o, const store_hdr &, u32 t) { off.push_back(o); type.push_back(t); })) { printf("not a store\n"); return 1; }
+  const size_t n = off.size();
+  CHECK(sigv.size() == n && s.records == n);
+  u32 bits = 1;
+  while (((size_t)1 << bits) < 2 * n + 2) bits++;
+  const size_t cap = (size_t)1 << bits;
+  std::vector<u64> keys(cap + 1, STORE_EMPTY_KEY), rkeys(cap + 1, STORE_EMPTY_KEY);
+  std::vector<u32> vals(cap + 1, STORE_NONE), rvals(cap + 1, STORE_NONE);
+  for (size_t i = 0; i < n; i++) {
+    store_index_one(buf, len, off[i], (u32)i, keys.data(), vals.data(), bits);
+    store_index_one(buf, len, off[n - 1 - i], (u32)(n - 1 - i), rkeys.data(), rvals.data(), bits);
+  }
+  std::vector<int8_t> verdict(n);
+  std::vector<u8> signer(33 * n + 1);
+  for (size_t i = 0; i < n; i++) {
+    const int pre = store_precheck_one<4>(T4, buf, len, off[i]);
+    CHECK(pre == store_precheck_one<8>(T8, buf, len, off[i]));
+    u8 rid[33];
+    const u32 aux = store_signer_one(buf, len, off.data(), (u32)i, keys.data(), vals.data(), bits, &signer[33 * i]);
+    CHECK(aux == store_signer_one(buf, len, off.data(), (u32)i, rkeys.data(), rvals.data(), bits, rid) && !memcmp(rid, &signer[33 * i], 33));
+    const bool has_sig = type[i] == STORE_T_CANN || type[i] == STORE_T_NANN || type[i] == STORE_T_CUPD;
+    verdict[i] = (int8_t)store_merge_one(pre, has_sig, (int8_t)sigv[i], aux);
+  }
+  free(buf);
+  const u64 w[5] = {s.records, s.live, s.deleted, s.end_offset, (u64)s.end_reason};
+  write_file(base + ".off", off.data(), 8 * n);
+  write_file(base + ".verdict", verdict.data(), n);
+  write_file(base + ".signer", signer.data(), 33 * n);
+  write_file(base + ".walk", w, sizeof w);
+  if (failures) return 1;
+  printf("ok\n");
+  return 0;
+}
+
+int main(int argc, char **argv) {
   static u32 T4[4 * 256], T8[8 * 256];
   store_crc_build_tables(T4, 4);
   store_crc_build_tables(T8, 8);
+  if (argc == 4) return audit_file(argv[1], argv[2], argv[3], T4, T8);
   CHECK(T4[1] == 0xF26B8303u);                                                  // the first entry of every published CRC-32C table
   {
     const u8 *digits = (const u8 *)"123456789";

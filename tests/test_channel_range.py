@@ -43,21 +43,21 @@ def digest_equals_model(eng, blob, verdict=None):
     return dg, want
 
 
-def replies_have_the_properties(want, q, status, replies):
+def replies_have_the_properties(want, q, status, replies, ours=crm.CHAIN):
     """what BOLT #7 and the split's contract ask of the replies to one query"""
     p = crm.parse_query(q)
     if p is None:
         assert status == -1 and replies == []
         return
     chain, first, number, option = p
-    if chain != crm.CHAIN:
+    if chain != ours:
         assert status == 1 and replies == [crm.encode(chain, first, number, [], 0, 0)[:43] + b"\x00\x00"]
         return
     assert status == 0 and len(replies) >= 1
     number = crm.fix_number(first, number)
     sel = crm.gather_range(want, first, number)
     ds = [crm.decode_reply(r) for r in replies]
-    assert all(len(r) <= 65535 for r in replies) and all(d["chain"] == crm.CHAIN for d in ds)
+    assert all(len(r) <= 65535 for r in replies) and all(d["chain"] == ours for d in ds)
     assert [s for d in ds for s in d["scids"]] == [e[0] for e in sel]                       # the replies concatenate to the sorted selection
     assert sum(d["blocks"] for d in ds) == number and ds[0]["first"] == first               # their blocks sum to the (fixed-up) request
     assert all(a["first"] + a["blocks"] == b["first"] for a, b in zip(ds, ds[1:]))          # first_blocknums chain
@@ -70,14 +70,14 @@ def replies_have_the_properties(want, q, status, replies):
         assert [c for d in ds for c in d["csum"]] == [e[2] for e in sel]
 
 
-def answers_equal_model(eng, dg, want, queries, cap=0):
-    status, replies = eng.channel_range_replies(dg, crm.CHAIN, queries, max_encoded_bytes=cap)
+def answers_equal_model(eng, dg, want, queries, cap=0, chain=crm.CHAIN):
+    status, replies = eng.channel_range_replies(dg, chain, queries, max_encoded_bytes=cap)
     assert len(status) == len(replies) == len(queries)
     memo = {}
     for k, q in enumerate(queries):
         if q not in memo:
-            memo[q] = crm.replies(want, crm.CHAIN, q, cap)
-            replies_have_the_properties(want, q, int(status[k]), replies[k])
+            memo[q] = crm.replies(want, chain, q, cap)
+            replies_have_the_properties(want, q, int(status[k]), replies[k], chain)
         assert (int(status[k]), replies[k]) == memo[q], (k, q.hex(), int(status[k]), memo[q][0], len(replies[k]), len(memo[q][1]))
     return status, replies
 

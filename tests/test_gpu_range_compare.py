@@ -26,10 +26,10 @@ def eng():
         yield e
 
 
-def compare_equals_model(eng, dg, entries, bare, msgs, want=None, mu=0, ms=0):
+def compare_equals_model(eng, dg, entries, bare, msgs, want=None, mu=0, ms=0, chain=crm.CHAIN):
     """-> the model's (status, per_msg, unknown, stale, flags, messages), which the device must equal"""
-    status, per_msg, unknown, stale, flags, out, s = eng.channel_range_compare(dg, crm.CHAIN, msgs, want=want, max_unknown=mu, max_stale=ms, return_summary=True)
-    model = rcm.compare(entries, bare, crm.CHAIN, msgs, want, mu, ms)
+    status, per_msg, unknown, stale, flags, out, s = eng.channel_range_compare(dg, chain, msgs, want=want, max_unknown=mu, max_stale=ms, return_summary=True)
+    model = rcm.compare(entries, bare, chain, msgs, want, mu, ms)
     got = ([int(x) for x in status], [tuple(int(x) for x in r) for r in per_msg], [int(x) for x in unknown], [int(x) for x in stale], [int(x) for x in flags], out)
     for name, a, b in zip(("status", "per_msg", "unknown", "stale", "flags", "messages"), got, model):
         assert a == b, (name, len(a), len(b), a[:6], b[:6])

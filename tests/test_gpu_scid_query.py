@@ -43,10 +43,10 @@ def build(eng, blob, verdict=None, **kw):
     return dr, m
 
 
-def answers_equal_model(eng, dr, m, queries):
+def answers_equal_model(eng, dr, m, queries, chain=crm.CHAIN):
     """-> the model's (status, per_query, messages, records), which the device must equal"""
-    status, per_query, msgs, recs, s = eng.short_channel_ids_replies(dr, queries, crm.CHAIN, return_records=True, return_summary=True)
-    model = sqm.answers(m, queries)
+    status, per_query, msgs, recs, s = eng.short_channel_ids_replies(dr, queries, chain, return_records=True, return_summary=True)
+    model = sqm.answers(m, queries, chain)
     got = ([int(x) for x in status], [tuple(int(x) for x in r) for r in per_query], msgs, recs)
     for name, a, b in zip(("status", "per_query", "messages", "records"), got, model):
         assert a == b, (name, len(a), len(b), a[:4], b[:4])

@@ -45,12 +45,12 @@ def build(eng, blob, verdict=None, recs=None, image=None):
     return ss, m
 
 
-def answers_equal_model(eng, ss, m, filters, now=NOW, cursors=None, budgets=None):
+def answers_equal_model(eng, ss, m, filters, now=NOW, cursors=None, budgets=None, chain=crm.CHAIN):
     """-> the model's (status, cursor_out, done, messages, records), which the device must equal"""
     if cursors is not None:
         cursors = [tfm.AS_FILTER if c is None else c for c in cursors]
-    status, cur, done, msgs, recs, s = eng.timestamp_filter_replies(ss, filters, crm.CHAIN, now, cursors, budgets, return_summary=True, return_records=True)
-    model = tfm.answers(m, filters, crm.CHAIN, now, cursors, budgets)
+    status, cur, done, msgs, recs, s = eng.timestamp_filter_replies(ss, filters, chain, now, cursors, budgets, return_summary=True, return_records=True)
+    model = tfm.answers(m, filters, chain, now, cursors, budgets)
     got = ([int(x) for x in status], [int(x) for x in cur], [int(x) for x in done], msgs, recs)
     for name, a, b in zip(("status", "cursor_out", "done", "messages", "records"), got, model):
         assert a == b, (name, len(a), len(b), a[:4], b[:4])

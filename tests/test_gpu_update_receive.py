@@ -37,10 +37,10 @@ def hand(orc):
 class Resident:
     """the digest and the directory of an image, and the model's view of it"""
 
-    def __init__(self, eng, blob, verdict=None):
+    def __init__(self, eng, blob, verdict=None, chain=crm.CHAIN):
         self.eng, self.blob, self.v = eng, blob, urm.view(blob, verdict)
         self.dg = eng.gossip_store_digest(blob, verdict=verdict)
-        self.dr = eng.gossip_store_directory(self.dg, blob, verdict=verdict, chain_hash=crm.CHAIN)
+        self.dr = eng.gossip_store_directory(self.dg, blob, verdict=verdict, chain_hash=chain)
 
     def close(self):
         self.dr.free()

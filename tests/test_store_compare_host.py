@@ -3,7 +3,8 @@ buffer it hands over is a heap block of exactly its size): the program's own che
 corpus for reply_channel_range (tests/golden/reply_channel_range_corpus.bin), one reply cut at every length and every status case, on which the
 header and the sequential model of range_compare_model must agree; and classification, merge and the query_short_channel_ids bytes against the model
 for hand-built stores and the golden ones -- the entries visited in file order, in reverse and in a scrambled order, the output written at all four
-alignments (the program compares those itself).  The device side of the same call, lamd_channel_range_compare_batch, is test_gpu_range_compare's."""
+alignments (the program compares those itself).  The device side of the same call, lamd_channel_range_compare_batch, is test_gpu_range_compare's.
+Last, the reply vector and the stores the reference ships (test_reference_stores)."""
 import os
 import struct
 import subprocess
@@ -15,6 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import channel_range_model as crm  # noqa: E402
 import range_compare_model as rcm  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_audit as sa  # noqa: E402
 
 ROOT = sa.ROOT
@@ -56,11 +58,11 @@ def host_compare(exe, d, blob, msgs, chain=crm.CHAIN, want=None, max_unknown=0, 
             [int(x) for x in arr("bare", "<u8")])
 
 
-def check_against_model(exe, d, blob, msgs, want=None, max_unknown=0, max_stale=0, verdict=None):
+def check_against_model(exe, d, blob, msgs, want=None, max_unknown=0, max_stale=0, verdict=None, chain=crm.CHAIN):
     entries = crm.sorted_digest(blob, verdict)[0] if blob is not None else []
     bare = rcm.bare(blob, verdict) if blob is not None else []
-    got = host_compare(exe, d, blob, msgs, crm.CHAIN, want, max_unknown, max_stale, verdict)
-    model = rcm.compare(entries, bare, crm.CHAIN, msgs, want, max_unknown, max_stale)
+    got = host_compare(exe, d, blob, msgs, chain, want, max_unknown, max_stale, verdict)
+    model = rcm.compare(entries, bare, chain, msgs, want, max_unknown, max_stale)
     assert got[6] == bare
     for name, a, b in zip(("status", "per_msg", "unknown", "stale", "flags", "messages"), got, model):
         assert a == b, (name, a[:8], b[:8])
@@ -150,3 +152,28 @@ def test_host_digest_with_verdicts_and_want(exe, tmp_path):
     want = [(0, 0xFFFFFFFF) if k % 3 else (0, 5) for k in range(len(msgs))]                  # every third query ends at block 5: most replies miss it
     got = check_against_model(exe, tmp_path / "v", blob, msgs, want=want, verdict=verdict)
     assert {0, 1, 4} <= set(got[0])
+
+
+@pytest.mark.parametrize("name", ["mainnet", "canned"])
+def test_host_compare_over_the_stores_the_reference_ships(exe, tmp_path, orc, name):
+    blob = rs.store(name)
+    chain, v = rs.chain_of(blob), sa.model(orc, blob)[1]
+    entries, bare = crm.sorted_digest(blob, v)[0], rcm.bare(blob, v)
+    assert (len(entries), len(bare)) == ((4, 84) if name == "mainnet" else (2, 0))
+    msgs = rcm.probe_replies(entries, bare, chain) + [c[0] for c in rcm.status_cases(chain)]
+    m = check_against_model(exe, tmp_path / "probe", blob, msgs, verdict=v, chain=chain)
+    assert {0, 1} <= set(m[0]) and m[2] and m[3] and (not bare or set(bare) & set(m[3]))
+    check_against_model(exe, tmp_path / "chunks", blob, msgs, max_unknown=3, max_stale=2, chain=chain)
+
+
+def test_host_compare_of_the_vector_reply(exe, tmp_path):
+    rep = rs.vectors()["extended_queries"][2]
+    chain, first, number, _, scids, ts, _ = rs.reply_fields(rep)
+    msg, want = bytes.fromhex(rep["hex"]), [(122334, 123834)]
+    m = check_against_model(exe, tmp_path / "empty", None, [msg], want=want, chain=chain)
+    assert (m[0], m[2], m[3]) == ([0], scids, [])
+    known, ours = rs.scid("0x7x30934"), (489645, 4786863)
+    blob = sa.serialise(0x10, [crm.rec(crm.cann(known)), crm.rec(crm.AMOUNT), crm.rec(crm.cupd(known, 0, ours[0]), ours[0]), crm.rec(crm.cupd(known, 1, ours[1]), ours[1])])
+    m = check_against_model(exe, tmp_path / "known", blob, [msg], want=want, chain=chain)
+    assert ts[1] == (489645, 4786864) and (m[0], m[2], m[3], m[4]) == ([0], [scids[0], scids[2]], [known], [4])
+    assert check_against_model(exe, tmp_path / "outside", blob, [msg], want=[(0, 100)], chain=chain)[0] == [4]

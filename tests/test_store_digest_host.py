@@ -3,7 +3,8 @@ hands over is a heap block of exactly its size): the program's own checks of big
 of the golden stores, of the synthetic store (with and without verdicts), of its damaged copy and of hand-built stores, built stage by stage in file
 order, in reverse and in a scrambled order of the records (the program compares the three itself), which must equal the sequential model of
 channel_range_model -- as must the bytes of the replies to every query set, written at all four alignments of the output.  The device side of the same
-calls, lamd_gossip_store_digest_build and lamd_channel_range_reply_batch, is test_channel_range's."""
+calls, lamd_gossip_store_digest_build and lamd_channel_range_reply_batch, is test_channel_range's.  Last, the stores and vectors the reference ships
+(test_reference_stores): the mainnet excerpt, the canned store, the two query vectors and the two update checksums."""
 import os
 import struct
 import subprocess
@@ -14,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import channel_range_model as crm  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_audit as sa  # noqa: E402
 from test_store_audit import damaged, synthetic  # noqa: E402,F401  (fixtures)
 
@@ -61,12 +63,12 @@ def host_answers(exe, d, blob, verdict, queries, cap, chain=crm.CHAIN):
     return entries, counters, status, replies
 
 
-def check_against_model(exe, d, blob, verdict, queries, cap):
+def check_against_model(exe, d, blob, verdict, queries, cap, chain=crm.CHAIN):
     want, wc = crm.sorted_digest(blob, verdict)
-    entries, counters, status, replies = host_answers(exe, d, blob, verdict, queries, cap)
+    entries, counters, status, replies = host_answers(exe, d, blob, verdict, queries, cap, chain)
     assert entries == want and counters == wc
     for k, q in enumerate(queries):
-        ws, wr = crm.replies(want, crm.CHAIN, q, cap)
+        ws, wr = crm.replies(want, chain, q, cap)
         assert (status[k], replies[k]) == (ws, wr), (k, q.hex(), status[k], ws, len(replies[k]), len(wr))
     return want
 
@@ -131,3 +133,31 @@ def test_host_parser_cases(exe, tmp_path):
     for v in list(range(8)) + [0x100, 0x10003]:
         d = crm.decode_reply(replies[queries.index(crm.query(crm.CHAIN, 5, 9, v))][0])
         assert (d["ts"] is not None, d["csum"] is not None) == (bool(v & 1), bool(v & 2)) and len(d["scids"]) == 2
+
+
+@pytest.mark.parametrize("name,entries,bare", [("mainnet", 4, 84), ("canned", 2, 0)])
+def test_host_digest_and_replies_of_the_stores_the_reference_ships(exe, tmp_path, orc, name, entries, bare):
+    blob = rs.store(name)
+    chain = rs.chain_of(blob)
+    blocks = [e[0] >> 40 for e in crm.digest(blob)[0]]
+    want = check_against_model(exe, tmp_path / "plain", blob, None, crm.query_kinds(blocks, chain), 0, chain)
+    assert check_against_model(exe, tmp_path / "verdicts", blob, sa.model(orc, blob)[1], crm.mixed_queries(blocks, 65, chain), 8, chain) == want
+    assert len(want) == entries and crm.digest(blob)[1]["channels_no_update"] == bare
+
+
+def test_host_vector_queries_and_the_reference_checksums(exe, tmp_path):
+    vec = rs.vectors()
+    q1, q2 = vec["extended_queries"][:2]
+    chain = bytes.fromhex(q1["msg"]["chainHash"])
+    blocks = (34_999, 35_000, 35_099, 35_100, 99_999, 100_000, 101_499, 101_500)
+    blob = crm.channel_store([crm.scid_of(b, 1, 0) for b in blocks], both=True)
+    _, _, status, replies = host_answers(exe, tmp_path / "q", blob, None, [bytes.fromhex(q1["hex"]), bytes.fromhex(q2["hex"])], 0, chain)
+    d1, d2 = crm.decode_reply(replies[0][0]), crm.decode_reply(replies[1][0])
+    assert status == [0, 0] and [s >> 40 for s in d1["scids"]] == [100_000, 101_499] and [s >> 40 for s in d2["scids"]] == [35_000, 35_099]
+    assert d1["ts"] is None and d1["csum"] is None and d2["ts"] is not None and d2["csum"] is not None
+    ups = [bytes.fromhex(p["update"]) for p in vec["update_checksums"]]
+    recs = []
+    for k, m in enumerate(ups):
+        recs += [crm.rec(crm.cann(int.from_bytes(m[98:106], "big"), k)), crm.rec(crm.AMOUNT), crm.rec(m, int.from_bytes(m[106:110], "big"))]
+    want = check_against_model(exe, tmp_path / "c", sa.serialise(0x10, recs), None, [crm.query(crm.CHAIN, 0, 0xFFFFFFFF, 2)], 0)
+    assert [e[2] for e in want] == [(p["checksum"], 0) for p in vec["update_checksums"]] == [(0x1112fa30, 0), (0xf32ce968, 0)]

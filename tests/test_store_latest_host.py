@@ -3,7 +3,7 @@ buffer it hands over is a heap block of exactly its size): the program's own che
 new reason on a hand-built store; and the latest-wins repair of the hand-built stores of test_store_latest and of the synthetic store with injected
 duplicates, whose reasons, new offsets and output bytes must equal the sequential model of test_store_latest -- in file order, in reverse and in a
 scrambled order of the records (the program compares the three itself).  The device side of the same call, lamd_gossip_store_repair_latest, is
-test_store_latest's."""
+test_store_latest's.  Last, the stores the reference ships (test_reference_stores) against the same model."""
 import os
 import struct
 import subprocess
@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_store_audit as sa  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_latest as sl  # noqa: E402
 from test_store_audit import synthetic  # noqa: E402,F401  (fixture)
 from test_store_latest import stores  # noqa: E402,F401  (fixture)
@@ -74,3 +75,14 @@ def test_host_repair_of_the_store_with_injected_duplicates_equals_the_model(exe,
         n = want[0].count(sl.KEPT) + 1
         again = _host_repair(exe, tmp_path / ("again%d" % k), want[2], [0] * n, sl.UUID, **pol)
         assert again[2] == want[2] and again[0] == [sl.R_BOOKKEEPING] + [sl.KEPT] * (n - 1)
+
+
+@pytest.mark.parametrize("name", ["part1", "mainnet", "fixed", "canned"])
+def test_host_repair_of_the_stores_the_reference_ships_equals_the_model(exe, tmp_path, orc, name):
+    """the mainnet excerpt and the canned store of test_reference_stores, without a clock and at their own: the newest header timestamp + 1"""
+    blob = rs.store(name)
+    v = sa.model(orc, blob)[1]
+    for k, pol in enumerate((sl.OFF, dict(CLOCK, now=rs.newest(blob) + 1))):
+        want = sl.latest_model(blob, v, sl.UUID, **pol)
+        assert _host_repair(exe, tmp_path / str(k), blob, v, sl.UUID, **pol) == want
+        assert not {sl.R_SUPERSEDED, sl.R_TIMESTAMP, sl.R_STALE} & set(want[0]) and want[0].count(sl.KEPT) == rs.KEPT[name]

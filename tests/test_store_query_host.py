@@ -4,8 +4,9 @@ buffer it hands over is a heap block of exactly its size): the reference's fuzz 
 model of scid_query_model must agree; and the directory and the answers against the model for the golden stores, the slot store, the hand-built
 store and a store in three record orders, with and without verdicts -- the records and the occurrences visited in file order, in reverse and
 in a scrambled order, the output written at all four alignments (the program compares those itself).  The device side of the same calls,
-lamd_gossip_store_directory_build and lamd_short_channel_ids_reply_batch, is test_gpu_scid_query's.  The last test here pins the new
-prototypes of include/lightning_amd.h to their ctypes bindings."""
+lamd_gossip_store_directory_build and lamd_short_channel_ids_reply_batch, is test_gpu_scid_query's.  One test pins the new
+prototypes of include/lightning_amd.h to their ctypes bindings; the last ones run the query vector and the stores the reference ships
+(test_reference_stores)."""
 import ctypes
 import os
 import random
@@ -20,6 +21,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import channel_range_model as crm  # noqa: E402
 import scid_query_model as sqm  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_audit as sa  # noqa: E402
 
 ROOT = sa.ROOT
@@ -56,14 +58,14 @@ def host_run(exe, d, blob, queries, chain=crm.CHAIN, verdict=None):
                 bare_rec=[int(x) for x in arr("barerec", "<u4")], ranks=[int(x) for x in arr("ranks", "<u4")], counters=[int(x) for x in arr("counters", "<u8")])
 
 
-def check_against_model(exe, d, blob, queries, verdict=None):
-    got = host_run(exe, d, blob, queries, crm.CHAIN, verdict)
+def check_against_model(exe, d, blob, queries, verdict=None, chain=crm.CHAIN):
+    got = host_run(exe, d, blob, queries, chain, verdict)
     m = sqm.directory(blob, verdict)
     assert (got["nodes"], got["first"], got["nann"], got["bare_rec"]) == (m["nodes"], m["first"], m["nann"], m["bare_rec"])
     assert got["ranks"] == [r for s in m["entries"] + m["bare"] for r in m["ranks"][s]]
     c = m["counters"]
     assert got["counters"] == [c["nodes"], c["nodes_announced"], c["nann_no_node"], c["nann_in_front"], c["nann_short"]]
-    status, per_query, msgs, recs = sqm.answers(m, queries)
+    status, per_query, msgs, recs = sqm.answers(m, queries, chain)
     for name, a, b in zip(("status", "per_query", "msgs", "recs"), (got["status"], got["per_query"], got["msgs"], got["recs"]), (status, per_query, msgs, recs)):
         assert a == b, (name, a[:4], b[:4])
     return m, got
@@ -213,3 +215,26 @@ def test_new_prototypes_and_bindings_agree(tmp_path):
         want.append(ctypes.sizeof(cls))
         want += [getattr(cls, f[0]).offset for f in cls._fields_]
     assert out == want, (out, want)
+
+
+@pytest.mark.parametrize("name", ["mainnet", "canned"])
+def test_host_directory_and_answers_for_the_stores_the_reference_ships(exe, tmp_path, orc, name):
+    blob = rs.store(name)
+    chain, v = rs.chain_of(blob), sa.model(orc, blob)[1]
+    d = sqm.directory(blob, v)
+    m, got = check_against_model(exe, tmp_path / "flags", blob, sqm.flag_queries(d, chain), v, chain)
+    announced = [r for r in m["nann"] if r != sqm.NONE]
+    assert (len(m["nodes"]), len(announced), len(m["chan"])) == ((126, 0, 88) if name == "mainnet" else (3, 3, 2))
+    assert m["nodes"] == sorted(set(m["nodes"])) and set(got["status"]) == {0}
+    sent = [x for ms in got["msgs"] for x in ms if x[:2] == b"\x01\x01"]
+    assert bool(sent) == bool(announced) and set(sent) == {m["recs"][r][4] for r in announced}
+
+
+def test_host_answer_to_the_vector_query(exe, tmp_path):
+    q = rs.vectors()["extended_queries"][3]
+    chain, known = bytes.fromhex(q["msg"]["chainHash"]), rs.scid("0x0x15465")
+    blob = crm.channel_store([known], both=True)
+    m, got = check_against_model(exe, tmp_path / "q", blob, [bytes.fromhex(q["hex"])], chain=chain)
+    recs = sa.walk(blob)[0]
+    assert got["status"] == [0] and got["per_query"] == [(3, 1, 3, 0)]
+    assert got["msgs"] == [[recs[0][4], recs[2][4], recs[3][4], struct.pack(">H", 262) + chain + b"\x01"]]

@@ -6,7 +6,8 @@ and flag; the messages, rows and sorted positions visited in arrival order, in r
 alignments (the program compares those itself).  The signature verdicts are an input computed by the oracle: the stages on both sides of the
 signature batch are what is under test here; the device side, signature batch included, is test_gpu_update_receive's.  Two further tests: the
 plan applied to the image of a live GossipIngest equals the image that ingest holds after it has processed the same batch; and the new
-prototype of include/lightning_amd.h agrees with its ctypes binding."""
+prototype of include/lightning_amd.h agrees with its ctypes binding.  Last, the updates of the stores the reference ships (test_reference_stores),
+foreign signatures and all, received against those stores."""
 import ctypes
 import os
 import random
@@ -21,6 +22,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import channel_range_model as crm  # noqa: E402
 import gossip_stream as gs  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_audit as sa  # noqa: E402
 import update_receive_model as urm  # noqa: E402
 from test_store_audit import damaged, synthetic  # noqa: E402,F401  (fixtures)
@@ -247,3 +249,26 @@ def test_new_prototype_and_binding_agree(tmp_path):
     out = [int(x) for x in subprocess.check_output([str(tmp_path / "layout")]).split()]
     assert out == [ctypes.sizeof(cls)] + [getattr(cls, f[0]).offset for f in cls._fields_]
     assert hasattr(_ffi.load(), n)
+
+
+@pytest.mark.parametrize("name", ["mainnet", "part1", "canned"])
+def test_the_stores_the_reference_ships_receive_their_own_updates(exe, tmp_path, orc, name):
+    """every channel_update found in the image (for part 1: in part 1 + part 2), the deleted ones included, in file order, then the same with one bit
+    of each signature flipped"""
+    blob = rs.store(name)
+    ups = rs.updates_in(rs.store("mainnet") if name == "part1" else blob)
+    msgs, chain = [m for _, _, m in ups], rs.chain_of(blob)
+    now = max(r[3] for r in sa.walk(rs.store("mainnet") if name == "part1" else blob)[0]) + 1
+    v, want = check_against_model(exe, tmp_path / "own", orc, blob, msgs, chain, now, verdict=sa.model(orc, blob)[1])
+    assert 6 not in want["status"] and sum(1 for s in want["signer"] if s is not None) == (rs.PART1_RECEIVE["signed"] if name == "part1" else len(msgs))
+    if name != "part1":
+        assert all(want["status"][k] == urm.DUPLICATE for k, u in enumerate(ups) if not u[1])
+    else:
+        assert want["status"].count(urm.UNKNOWN) == rs.PART1_RECEIVE["unknown"] and want["status"].count(urm.ACCEPTED) == rs.PART1_RECEIVE["accepted"]
+        assert sa.model(orc, urm.apply(blob, v, want))[2]["clean"] == 1
+    flipped = [m[:40] + bytes([m[40] ^ 1]) + m[41:] for m in msgs]
+    _, bad = check_against_model(exe, tmp_path / "flipped", orc, blob, flipped, chain, now)
+    assert urm.ACCEPTED not in bad["status"] and urm.BAD_SIGNATURE in bad["status"]
+    if name == "part1":                                                                          # what was accepted now fails its signature
+        assert all(b == urm.BAD_SIGNATURE for a, b in zip(want["status"], bad["status"]) if a == urm.ACCEPTED)
+        assert sum(1 for s in bad["signer"] if s is not None) == rs.PART1_RECEIVE["signed"] and bad["status"].count(urm.UNKNOWN) == rs.PART1_RECEIVE["unknown"]

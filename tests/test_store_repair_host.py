@@ -1,7 +1,8 @@
 """lightning_amd/csrc/store_repair.h on the host, under AddressSanitizer and UBSan (tests/c/store_repair_host.cpp, a stand-alone program: every
 buffer it hands over is a heap block of exactly its size): the program's own checks of the node table, of the copy at every source and output
 alignment and of every keep rule on a hand-built store; and the repair of the synthetic store of test_store_audit and of its damaged copy,
-whose keep flags, reasons, new offsets and output bytes must equal the Python model of test_store_repair (verdicts by test_store_audit.model)."""
+whose keep flags, reasons, new offsets and output bytes must equal the Python model of test_store_repair (verdicts by test_store_audit.model);
+and the same for the stores the reference ships (test_reference_stores)."""
 import os
 import subprocess
 import sys
@@ -11,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_store_audit as sa  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_repair as sr  # noqa: E402
 from test_store_audit import damaged, synthetic  # noqa: E402,F401  (fixtures)
 
@@ -68,3 +70,16 @@ def test_host_repair_of_the_reference_stores_equals_compactd(exe, tmp_path, orc)
         d.mkdir()
         blob = sa._golden(name)
         assert _host_repair(exe, d, blob, sa.model(orc, blob)[1], sr.UUID)[2] == sr.compactd_first_phase(blob, sr.UUID)
+
+
+@pytest.mark.parametrize("name", ["part1", "mainnet", "fixed", "canned"])
+def test_host_repair_of_the_stores_the_reference_ships_equals_the_model(exe, tmp_path, orc, name):
+    """the mainnet excerpt (its first part, both parts, both with the tombstone's CRC corrected) and the canned store of test_reference_stores"""
+    blob = rs.store(name)
+    verdicts = sa.model(orc, blob)[1]
+    want = sr.repair_model(blob, verdicts, sr.UUID)
+    assert _host_repair(exe, tmp_path, blob, verdicts, sr.UUID) == want
+    if name in ("part1", "canned"):
+        assert want[2] == sr.compactd_first_phase(blob, sr.UUID)
+    else:                                                 # the last announcement has the tombstone behind it, not an amount record
+        assert want[0][-2:] == [sr.R_DEPENDENCY, sr.R_VERDICT if name == "mainnet" else sr.R_BOOKKEEPING] and want[0].count(sr.KEPT) == rs.KEPT[name]

@@ -3,8 +3,8 @@ buffer it hands over is a heap block of exactly its size): the stream index of a
 the header and the sequential model of timestamp_filter_model must agree -- for the golden stores, the synthetic store with and without the
 verdicts of its damaged copy, and hand-built stores; the records, the peers and the lanes of every tile visited in file order, in reverse and
 in a scrambled order, the output written at all four alignments (the program compares those itself).  The device side of the same calls,
-lamd_gossip_store_stream_build and lamd_timestamp_filter_reply_batch, is test_gpu_timestamp_filter's.  The last test here pins the new
-prototypes of include/lightning_amd.h to their ctypes bindings."""
+lamd_gossip_store_stream_build and lamd_timestamp_filter_reply_batch, is test_gpu_timestamp_filter's.  One test pins the new
+prototypes of include/lightning_amd.h to their ctypes bindings; the last one runs the stores the reference ships (test_reference_stores)."""
 import ctypes
 import os
 import random
@@ -19,6 +19,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import channel_range_model as crm  # noqa: E402
 import scid_query_model as sqm  # noqa: E402
+import test_reference_stores as rs  # noqa: E402
 import test_store_audit as sa  # noqa: E402
 import timestamp_filter_model as tfm  # noqa: E402
 from test_store_audit import damaged, synthetic  # noqa: E402,F401  (fixtures)
@@ -61,10 +62,10 @@ def host_run(exe, d, blob, filters, now=NOW, cursors=None, budgets=None, verdict
                 msgs=[[out[int(off[j]):int(off[j + 1])] for j in sp] for sp in spans], recs=[[int(rec[j]) for j in sp] for sp in spans])
 
 
-def check_against_model(exe, d, blob, filters, now=NOW, cursors=None, budgets=None, verdict=None, recs=None, image=None):
+def check_against_model(exe, d, blob, filters, now=NOW, cursors=None, budgets=None, verdict=None, recs=None, image=None, chain=crm.CHAIN):
     """image: the bytes handed over when they are not all of blob (a cut image); recs: what stands for rec_off"""
     img = blob if image is None else image
-    got = host_run(exe, d, img, filters, now, cursors, budgets, verdict, None if recs is None else [r[0] for r in recs])
+    got = host_run(exe, d, img, filters, now, cursors, budgets, verdict, None if recs is None else [r[0] for r in recs], chain)
     m = tfm.index(blob, verdict, recs, len(img))
     assert (got["srec"], got["sts"], got["slen"]) == ([e[0] for e in m["list"]], [e[1] for e in m["list"]], [len(e[2]) for e in m["list"]])
     assert got["spos"] == m["spos"] and got["counters"] == [m["counters"][k] for k in tfm.COUNTERS]
@@ -73,7 +74,7 @@ def check_against_model(exe, d, blob, filters, now=NOW, cursors=None, budgets=No
         run = max(run, ts)
         pm.append(run)
     assert got["pmax"] == pm
-    want = tfm.answers(m, filters, crm.CHAIN, now, cursors, budgets)
+    want = tfm.answers(m, filters, chain, now, cursors, budgets)
     for name, a, b in zip(("status", "cursor", "done", "msgs", "recs"), (got[k] for k in ("status", "cursor", "done", "msgs", "recs")), want):
         assert a == b, (name, a[:4], b[:4])
     return m, want
@@ -234,3 +235,16 @@ def test_new_prototypes_and_bindings_agree(tmp_path):
         want.append(ctypes.sizeof(cls))
         want += [getattr(cls, f[0]).offset for f in cls._fields_]
     assert out == want, (out, want)
+
+
+@pytest.mark.parametrize("name,streamable", [("mainnet", 92), ("canned", 9)])
+def test_host_index_and_answers_for_the_stores_the_reference_ships(exe, tmp_path, orc, name, streamable):
+    blob = rs.store(name)
+    chain, v, now = rs.chain_of(blob), sa.model(orc, blob)[1], rs.newest(blob) + 100
+    everything = tfm.filt(chain, 0, 0xFFFFFFFF)
+    m, want = check_against_model(exe, tmp_path / "corpus", blob, tfm.corpus(chain) + [everything], now, verdict=v, chain=chain)
+    assert m["counters"]["streamable"] == streamable == len(want[3][-1]) and set(want[0]) == {-1, 0, 1}
+    # a budget of 1 000 bytes from every position: what a resumed peer is sent next
+    n = len(m["list"])
+    _, want = check_against_model(exe, tmp_path / "resumed", blob, [everything] * (n + 1), now, list(range(n + 1)), [1000] * (n + 1), chain=chain)
+    assert want[2][-1] == 1 and want[2][0] == 0 and all(r == [e[0] for e in m["list"][c:c + len(r)]] for c, r in enumerate(want[4]))
