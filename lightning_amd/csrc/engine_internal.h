@@ -117,6 +117,7 @@ struct lamd_ctx {
   // hk[1]: 10 teeth -- representative row, cache entry, table slot; parsed key, validity, build scratch), row lists per shape + cold rows
   devbuf row_ent, kd_table, kd_rep, kd_uid, kd_uniq, kd_count, kd_newent, plan, kt_fin;
   struct shape_ws { devbuf row, ent, slot, qwords, keyok, scratch; } hk[2];
+  devbuf kc_chains;               // the finish kernel's per-chain words: KC_CHAIN_CHUNKS 16-byte chunks per thread of its resident grid, interleaved over a block (verify_core.h kc_lanes)
   devbuf list7, list10, listcold, listcold_ok;
   // latency path (k_small_verify): pinned, device-mapped staging for up to SMALL_MAX rows, the verdict bytes and the completion word
   u8 *h_small = nullptr;
@@ -180,6 +181,7 @@ struct lamd_ctx {
   bool early_cold = true;         // LAMD_EARLY_COLD=0: the cold rows' list is made by k_partition, after the table kernels (rounds 1-5)
   bool fused_front = true;        // LAMD_FUSED_FRONT=0: the front end of a keyed call as the 19 launches + 5 fills of round 2 (see k_call_init)
   bool kc_tree = false;           // LAMD_KC_TREE=1: key tables by the affine tree builder (k_kc_tree_both) instead of the Gray-code chains (k_kc_finish_both); read on the root context
+  unsigned table_grid = 0;        // LAMD_TABLE_GRID: blocks of the resident grids of k_keys_bases_both / k_kc_finish_both (0: one per compute unit -- table_grid()); read on the root context
   bool small_fused = true;        // LAMD_SMALL_FUSED=0: small batches take the partitioning path even with a cache
   bool last_small_fused = false;  // the previous small batch of this lane ran k_ecmult_small (its plan holds P_DENSE)
   size_t last_small_n = 0;

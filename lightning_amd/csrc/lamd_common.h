@@ -9,9 +9,11 @@
 #include <hip/hip_runtime.h>
 #define LAMD_HD __host__ __device__ __forceinline__
 #define LAMD_HD_NOINLINE __host__ __device__ __noinline__
+#define LAMD_HD_MEMBER __host__ __device__ __forceinline__   // (member functions: the host form of LAMD_HD says `static`)
 #else
 #define LAMD_HD static inline __attribute__((always_inline))
 #define LAMD_HD_NOINLINE static __attribute__((noinline))
+#define LAMD_HD_MEMBER inline __attribute__((always_inline))
 #endif
 
 #if defined(LAMD_CHECK_MAG)

@@ -615,9 +615,14 @@ struct kc_shape_args {
   const u32 *hk_ent, *hk_slot;
   u32 *qwords;             // parsed key, 16 words per key
   u8 *keyok;
-  u32 *scratch;
+  u32 *scratch;            // the fused front end's kernels: key u's words in group u / 64 of kc_key_chunks(T) * 64 chunks, interleaved (kc_key_view); the others: flat
   u32 *pool;
 };
+// key u's slots in the wave-interleaved scratch of its shape
+template <int T>
+__device__ __forceinline__ kc_lanes kc_key_view(u32 *scratch, size_t u) {
+  return kc_lanes{scratch + (u / 64u) * (size_t)(64 * 4 * kc_key_chunks(T)), 64, u % 64u};
+}
 template <int T>
 static void launch_keytables(hipStream_t st, const u32 *plan, int which, const kc_shape_args &A) {
   const size_t cap = A.cap, chains = cap * kc_nsub(T);
@@ -629,12 +634,14 @@ static void launch_keytables(hipStream_t st, const u32 *plan, int which, const k
                      A.scratch);
 }
 
-// ---- the fused front end's two table kernels (see k_call_init).  One grid covers both comb shapes: blocks [0, blocks7) work on the
-// 7-tooth list, the others on the 10-tooth list.
-template <int T>
-__device__ __forceinline__ void keys_bases_body(size_t u, const u32 *__restrict__ plan, int which, const kc_shape_args &A, const u8 *__restrict__ keys,
-                                                int keylen, size_t stride) {
-  const u32 nkeys = plan[which] < A.cap ? plan[which] : A.cap;
+// ---- the fused front end's two table kernels (see k_call_init).  One grid covers both comb shapes, and it is a RESIDENT grid (round 8): the lists'
+// lengths are only known on the device (plan), so a grid that covers their upper bounds -- n / threshold + 1 keys per shape -- is mostly blocks that
+// read plan and leave (734 launched for 256 with keys, 5 210 for 1 024 at the headline's 65 536 keys), each of them a wave slot taken from the
+// ecmult kernel of the call before.  Instead a fixed number of blocks (table_grid) walks the work that exists: groups of 64 keys (bases, a wave
+// each) and of 256 (key, chain) threads (finish, a block each), the 7-tooth list's groups first, then the 10-tooth list's.  An empty list costs nothing.
+// (LANES: the keys' words wave-interleaved, for k_kc_finish_both; otherwise in the flat per-key areas k_kc_tree_both reads)
+template <int T, bool LANES>
+__device__ __forceinline__ void keys_bases_body(size_t u, u32 nkeys, const kc_shape_args &A, const u8 *__restrict__ keys, int keylen, size_t stride) {
   if (u >= nkeys) return;
   u32 qx[8], qy[8];
   const bool ok = parse_pubkey(keys + stride * (size_t)A.hk_row[u], keylen, qx, qy);
@@ -644,13 +651,22 @@ __device__ __forceinline__ void keys_bases_body(size_t u, const u32 *__restrict_
   dst[2] = make_uint4(qy[0], qy[1], qy[2], qy[3]);
   dst[3] = make_uint4(qy[4], qy[5], qy[6], qy[7]);
   A.keyok[u] = ok;
-  if (ok) kc_bases<T>(A.scratch + u * kc_scratch_words(T), ge_from_words(qx, qy));
+  if (!ok) return;
+  if constexpr (LANES) kc_bases_at<T>(kc_key_view<T>(A.scratch, u), ge_from_words(qx, qy));
+  else kc_bases<T>(A.scratch + u * kc_scratch_words(T), ge_from_words(qx, qy));
 }
-__global__ void __launch_bounds__(256) k_keys_bases_both(const u32 *__restrict__ plan, unsigned blocks7, kc_shape_args A7, kc_shape_args A10,
-                                                         const u8 *__restrict__ keys, int keylen, size_t stride) {
+template <bool LANES>
+__global__ void __launch_bounds__(256) k_keys_bases_both(const u32 *__restrict__ plan, kc_shape_args A7, kc_shape_args A10, const u8 *__restrict__ keys,
+                                                         int keylen, size_t stride) {
   LAMD_PRIO(8);
-  if (blockIdx.x < blocks7) keys_bases_body<7>((size_t)blockIdx.x * blockDim.x + threadIdx.x, plan, P_HK7, A7, keys, keylen, stride);
-  else keys_bases_body<10>((size_t)(blockIdx.x - blocks7) * blockDim.x + threadIdx.x, plan, P_HK10, A10, keys, keylen, stride);
+  const u32 n7 = plan[P_HK7] < A7.cap ? plan[P_HK7] : A7.cap, n10 = plan[P_HK10] < A10.cap ? plan[P_HK10] : A10.cap;
+  const u32 groups7 = (n7 + 63u) / 64u, groups = groups7 + (n10 + 63u) / 64u;  // (a shape that is off has cap 0)
+  const u32 lane = threadIdx.x & 63u, waves = gridDim.x * (blockDim.x / 64u);
+#pragma unroll 1
+  for (u32 g = blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; g < groups; g += waves) {
+    if (g < groups7) keys_bases_body<7, LANES>((size_t)g * 64u + lane, n7, A7, keys, keylen, stride);
+    else keys_bases_body<10, LANES>((size_t)(g - groups7) * 64u + lane, n10, A10, keys, keylen, stride);
+  }
 }
 // chains forward -> Z products (+ the key's cache entry) -> chains backward: the kc_nsub(T) chains of a key are neighbouring threads
 // of one block (256 is a multiple of 4 and of 32), the stages talk through the key's scratch area, a block barrier between them.
@@ -665,18 +681,37 @@ struct publish_args {
   u32 mask;
   int do_index;
 };
+// The cache entry's key words (key_words) written straight to the entry, and their key_words_hash: a local cache_ent would be an array under a
+// runtime index, which the compiler keeps in scratch memory (84 bytes of private segment per lane of the finish kernel until round 8).
+__device__ __forceinline__ u64 publish_key_words(cache_ent *dst, const u8 *p, int len, u64 seed) {
+  u64 h = seed;
+  u32 even = 0;
+#pragma unroll 1
+  for (int w = 0; w < 17; w++) {
+    u32 v = 0;
+    for (int b = 0; b < 4; b++) {
+      const int k = 4 * w + b;
+      if (k < len) v |= (u32)p[k] << (8 * b);
+    }
+    if (w == 16) v |= (u32)len << 8;
+    dst->kw[w] = v;
+    if (w == 16) h = splitmix64(h ^ v);
+    else if (w & 1) h = splitmix64(h ^ ((u64)even | ((u64)v << 32)));
+    else even = v;
+  }
+  return h;
+}
 template <int T>
-__device__ __forceinline__ void kc_finish_body(size_t t, const u32 *__restrict__ plan, int which, const kc_shape_args &A, const publish_args &P) {
+__device__ __forceinline__ void kc_finish_body(size_t t, u32 nkeys, const kc_shape_args &A, const publish_args &P, const kc_lanes &chain) {
   constexpr int NS = kc_nsub(T);
   static_assert(256 % NS == 0, "a key's chains must not straddle blocks");
   const size_t u = t / NS;
   const int sub = (int)(t % NS);
-  const u32 nkeys = plan[which] < A.cap ? plan[which] : A.cap;
   const bool live = u < nkeys;
   const bool ok = live && A.keyok[u];
   u32 *tab = ok ? A.pool + (size_t)A.hk_slot[u] * kc_stride(T) : nullptr;
-  u32 *scr = A.scratch + u * kc_scratch_words(T);
-  if (ok) kc_chain_fwd<T>(tab, scr, sub);
+  const kc_lanes key = kc_key_view<T>(A.scratch, u);
+  if (ok) kc_chain_fwd_at<T>(tab, key, chain, sub);
   // (block scope is all the stages need -- __syncthreads() carries the workgroup-scope release / acquire.  A device-scope __threadfence()
   // here writes the XCD's L2 back on every wave: the two table kernels took 3.9 ms instead of 1.9, measured in GPU session l.)
   __syncthreads();
@@ -685,19 +720,18 @@ __device__ __forceinline__ void kc_finish_body(size_t t, const u32 *__restrict__
       u32 qx[8], qy[8];
 #pragma unroll
       for (int i = 0; i < 8; i++) { qx[i] = A.qwords[u * 16 + i]; qy[i] = A.qwords[u * 16 + 8 + i]; }
-      kc_prefix<T>(tab, scr, ge_from_words(qx, qy));
+      kc_prefix_at<T>(tab, key, chain, ge_from_words(qx, qy));
     }
     // the key's cache entry (k_cache_publish): a key that does not parse is entered as such
-    cache_ent e;
-    key_words(e.kw, P.keys + P.stride * (size_t)A.hk_row[u], P.keylen);
-    e.meta = (ok ? (u32)T : 0u) | (P.lane << 8);
-    e.seq = P.seq;
-    e.tabslot = A.hk_slot[u];
     const u32 id = A.hk_ent[u];
-    P.ents[id] = e;
+    cache_ent *const e = P.ents + id;
+    const u64 hash = publish_key_words(e, P.keys + P.stride * (size_t)A.hk_row[u], P.keylen, P.seed);
+    e->meta = (ok ? (u32)T : 0u) | (P.lane << 8);
+    e->seq = P.seq;
+    e->tabslot = A.hk_slot[u];
     if (P.do_index) {
       __threadfence();
-      u32 slot = (u32)key_words_hash(e.kw, P.seed) & P.mask;
+      u32 slot = (u32)hash & P.mask;
       for (;;) {
         if (atomicCAS(&P.index[slot], 0u, id + 1u) == 0u) break;
         slot = (slot + 1u) & P.mask;
@@ -705,12 +739,22 @@ __device__ __forceinline__ void kc_finish_body(size_t t, const u32 *__restrict__
     }
   }
   __syncthreads();
-  if (ok) kc_chain_bwd<T>(tab, scr, sub);
+  if (ok) kc_chain_bwd_at<T>(tab, chain, sub);
 }
-__global__ void __launch_bounds__(256) k_kc_finish_both(const u32 *__restrict__ plan, unsigned blocks7, kc_shape_args A7, kc_shape_args A10, publish_args P) {
+// (every thread of a block runs the same iterations -- the extents come from plan -- and a block works on one shape per iteration: the two
+// barriers of the body are uniform.  A block's per-chain words -- chains: KC_CHAIN_CHUNKS chunks per thread, interleaved over the block -- serve every
+// iteration: a thread's chain slots are its own, and the one thread of a key that reads and writes its neighbours' (kc_prefix_at) does so between the two
+// barriers, which every neighbour reaches only after the backward pass of the iteration before.)
+__global__ void __launch_bounds__(256) k_kc_finish_both(const u32 *__restrict__ plan, kc_shape_args A7, kc_shape_args A10, publish_args P, u32 *chains) {
   LAMD_PRIO(8);
-  if (blockIdx.x < blocks7) kc_finish_body<7>((size_t)blockIdx.x * blockDim.x + threadIdx.x, plan, P_HK7, A7, P);
-  else kc_finish_body<10>((size_t)(blockIdx.x - blocks7) * blockDim.x + threadIdx.x, plan, P_HK10, A10, P);
+  const kc_lanes chain = {chains + (size_t)blockIdx.x * (256 * 4 * KC_CHAIN_CHUNKS), 256, threadIdx.x};
+  const u32 n7 = plan[P_HK7] < A7.cap ? plan[P_HK7] : A7.cap, n10 = plan[P_HK10] < A10.cap ? plan[P_HK10] : A10.cap;
+  const u64 groups7 = ((u64)n7 * kc_nsub(7) + 255u) / 256u, groups = groups7 + ((u64)n10 * kc_nsub(10) + 255u) / 256u;
+#pragma unroll 1
+  for (u64 g = blockIdx.x; g < groups; g += gridDim.x) {
+    if (g < groups7) kc_finish_body<7>((size_t)g * 256u + threadIdx.x, n7, A7, P, chain);
+    else kc_finish_body<10>((size_t)(g - groups7) * 256u + threadIdx.x, n10, A10, P, chain);
+  }
 }
 
 // The tree builder in the finish kernel's place (round 6, LAMD_KC_TREE=1; verify_core.h kc_tree_affine): one lane owns KPL keys of a shape -- four 7-tooth keys
@@ -1233,6 +1277,14 @@ static unsigned careful_grid(const lamd_ctx *ctx, size_t n) {
   return flood || blocks_for(n) < 64u ? blocks_for(n) : 64u;
 }
 
+// blocks of the resident grids of the two table kernels (k_keys_bases_both, k_kc_finish_both): what the chip holds at ONE block per compute unit --
+// they run in the wave slots the ecmult kernel of the call before leaves free, and a block that waits for a slot is no use to anybody -- and never more
+// than `bound`, the blocks that cover the lists' capacities.  LAMD_TABLE_GRID sets the number instead (the tests run the loops with 1 and 2 blocks).
+static unsigned table_grid(const lamd_ctx *root, unsigned bound) {
+  const unsigned want = root->table_grid ? root->table_grid : (unsigned)root->prop.multiProcessorCount;
+  return want < bound ? (want ? want : 1u) : bound;
+}
+
 // blocks of a table-driven ecmult launch: one thread per row (a capped grid leaves a tail of partly filled iterations: 3.19 ms -> 3.9 ms at 4 blocks per CU)
 static unsigned keyed_grid(size_t n) { return (unsigned)((n + KEYED_THREADS - 1) / KEYED_THREADS); }
 
@@ -1377,6 +1429,7 @@ extern "C" int lamd_init(lamd_ctx **out, int device) {
   if (const char *w = getenv("LAMD_FUSED_FRONT")) ctx->fused_front = atoi(w) != 0;
   if (const char *w = getenv("LAMD_EARLY_COLD")) ctx->early_cold = atoi(w) != 0;
   if (const char *w = getenv("LAMD_KC_TREE")) ctx->kc_tree = atoi(w) != 0;
+  if (const char *w = getenv("LAMD_TABLE_GRID")) ctx->table_grid = atoi(w) < 0 ? 0u : (unsigned)atoi(w);
   if (const char *w = getenv("LAMD_PREP_BATCH")) ctx->prep_batch = atoi(w) < 1 ? 1 : (size_t)atoi(w);
   if (const char *w = getenv("LAMD_PREP_MIN_THREADS")) ctx->prep_min_threads = atol(w) < 0 ? 0 : (size_t)atol(w);
   {
@@ -1993,7 +2046,7 @@ static int front_end_fused(lamd_ctx *ctx, lamd_ctx *root, const chunk_io &c, con
   if (on7 || on10) {
     const kc_shape_args A7 = shape_args(ctx->hk[0], on7 ? f.cap[0] : 0, kc->pool7), A10 = shape_args(ctx->hk[1], on10 ? f.cap[1] : 0, kc->pool10);
     const unsigned kb7 = on7 ? blocks_for(f.cap[0]) : 0u, kb10 = on10 ? blocks_for(f.cap[1]) : 0u;
-    hipLaunchKernelGGL(k_keys_bases_both, dim3(kb7 + kb10), dim3(256), 0, ctx->stream, (const u32 *)f.plan, kb7, A7, A10, c.d_key, c.keylen, c.keystride);
+    hipLaunchKernelGGL(root->kc_tree ? k_keys_bases_both<false> : k_keys_bases_both<true>, dim3(table_grid(root, kb7 + kb10)), dim3(256), 0, ctx->stream, (const u32 *)f.plan, A7, A10, c.d_key, c.keylen, c.keystride);
     const publish_args P = {c.d_key, c.keylen, c.keystride, (u32)ctx->lane_id, f.seq ? f.seq : 1u, root->hash_seed, kc->ents.as<cache_ent>(), kc->index.as<u32>(),
                             kc->index_mask, (int)f.use_cache};
     if (root->kc_tree) {
@@ -2002,7 +2055,9 @@ static int front_end_fused(lamd_ctx *ctx, lamd_ctx *root, const chunk_io &c, con
       hipLaunchKernelGGL(k_kc_tree_both, dim3(tb7 + tb10), dim3(64), 0, ctx->stream, (const u32 *)f.plan, tb7, A7, A10, P);
     } else {
       const unsigned fb7 = on7 ? blocks_for(f.cap[0] * kc_nsub(7)) : 0u, fb10 = on10 ? blocks_for(f.cap[1] * kc_nsub(10)) : 0u;
-      hipLaunchKernelGGL(k_kc_finish_both, dim3(fb7 + fb10), dim3(256), 0, ctx->stream, (const u32 *)f.plan, fb7, A7, A10, P);
+      const unsigned fgrid = table_grid(root, fb7 + fb10);
+      if ((rc = ensure(ctx, &ctx->kc_chains, (size_t)fgrid * 256 * KC_CHAIN_CHUNKS * 16)) != LAMD_OK) return rc;
+      hipLaunchKernelGGL(k_kc_finish_both, dim3(fgrid), dim3(256), 0, ctx->stream, (const u32 *)f.plan, A7, A10, P, ctx->kc_chains.as<u32>());
     }
   }
   if ((rc = mark_published(ctx, root, f)) != LAMD_OK) return rc;
@@ -2171,7 +2226,9 @@ static int chunk_partitioned(lamd_ctx *ctx, lamd_ctx *root, const chunk_io &c, b
       if ((rc = ensure(ctx, b, f.cap[s] * 4)) != LAMD_OK) return rc;
     if ((rc = ensure(ctx, &w.qwords, f.cap[s] * 64)) != LAMD_OK) return rc;
     if ((rc = ensure(ctx, &w.keyok, f.cap[s])) != LAMD_OK) return rc;
-    if ((rc = ensure(ctx, &w.scratch, f.cap[s] * kc_scratch_words(s ? 10 : 7) * 4)) != LAMD_OK) return rc;
+    // the keys' scratch: flat areas (stage-per-kernel launchers, tree builder) or whole groups of 64 wave-interleaved keys (the fused front end's kernels)
+    const size_t flat = f.cap[s] * kc_scratch_words(s ? 10 : 7) * 4, groups = (f.cap[s] + 63) / 64 * (size_t)(64 * 16 * kc_key_chunks(s ? 10 : 7));
+    if ((rc = ensure(ctx, &w.scratch, flat > groups ? flat : groups)) != LAMD_OK) return rc;
   }
   if ((rc = ensure(ctx, &ctx->plan, P_WORDS * 4)) != LAMD_OK) return rc;
   if (c.mode == MODE_SCHNORR && (rc = ensure(ctx, &ctx->kt_fin, n * (size_t)FIN_WORDS * 4)) != LAMD_OK) return rc;

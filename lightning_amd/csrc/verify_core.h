@@ -483,16 +483,84 @@ LAMD_HD void store_raw(u32 *dst, const fe &a) {
 //                            entry *= ratio^2 / ratio^3 and beta*x -- every entry an affine point of y^2 = x^3 + 7*Zc^6
 // No addition here can be degenerate: every operand is (odd integer < 2^136)*Q +- (even integer < 2^136)*Q with Q of
 // prime order n > 2^255.
-template <int T>
-LAMD_HD void kc_bases(u32 *scratch, const ge &q) {
+// Where the stages keep their intermediate words.  They address them in SLOTS -- one field element, 9 raw words; a key's slots: P0 (0..2) | Zb (3) |
+// C_i (4 + 2i, 5 + 2i) | stage 1's parking space; a chain's: Z_chain (0) | unify ratio (1) | H of addition g (1 + g) -- and a VIEW maps the slots of
+// the key or chain it stands for to memory:
+//   kc_flat   the contiguous area of kc_scratch_words(T) words per key described above, slot s of a view at word 9 s (host tests, the stage-per-kernel
+//             launchers, the tree builder, the latency path).  It has no room to park a chain's Jacobian X, Y: they wait in the table entry itself.
+//   kc_lanes  one lane of a group of `stride` lanes whose words are interleaved in 16-byte chunks -- chunk c of lane l at word (c * stride + l) * 4 of
+//             the group -- so that a wave's 16-byte accesses cover contiguous memory instead of 64 lines 3 KB apart, and the lanes of a key's chains,
+//             which read the same P0 and C_i, read the same chunk.  A slot takes 3 chunks (9 words, 3 of padding); behind a chain's slots the
+//             canonical X, Y of its 16 entries are parked (TW words each), so that the table entry is written once, finished, by kc_chain_bwd.
+struct alignas(16) kc_chunk { u32 w[4]; };
+constexpr int KC_SLOT_CHUNKS = 3, KC_PARK_CHUNKS = (TW + 3) / 4;
+constexpr int kc_key_slots(int T) { return 4 + 2 * (T - 1); }
+constexpr int KC_CHAIN_SLOTS = 2 + (KC_SUB - 1);
+static_assert(kc_key_slots(7) * 9 == kc_sub_off(7) && kc_key_slots(10) * 9 == kc_sub_off(10) && KC_CHAIN_SLOTS * 9 == KC_SUB_WORDS, "slots of the flat layout");
+// chunks per lane of a group of keys (with stage 1's parking space: 4 slots for each of its 2T-1 points) and of a group of chains
+constexpr int kc_key_chunks(int T) { return (kc_key_slots(T) + 4 * (2 * T - 1)) * KC_SLOT_CHUNKS; }
+constexpr int KC_CHAIN_CHUNKS = KC_CHAIN_SLOTS * KC_SLOT_CHUNKS + 2 * KC_SUB * KC_PARK_CHUNKS;
+struct kc_flat {
+  u32 *p;
+  static constexpr bool parks = false;
+  LAMD_HD_MEMBER fe load(int s) const { return slot_load_raw(p + 9 * s); }
+  LAMD_HD_MEMBER void store(int s, const fe &a) const { store_raw(p + 9 * s, a); }
+  LAMD_HD_MEMBER kc_flat after(int slots) const { return kc_flat{p + 9 * slots}; }
+  LAMD_HD_MEMBER kc_flat chain(int s) const { return kc_flat{p + s * KC_SUB_WORDS}; }  // chain s of the key whose chain 0 this view stands for
+  LAMD_HD_MEMBER fe unpark(int) const { return fe_set_int(0); }
+  LAMD_HD_MEMBER void park(int, const fe &) const {}
+};
+struct kc_lanes {
+  u32 *base;  // of the group, 16-byte aligned
+  size_t stride, lane;
+  static constexpr bool parks = true;
+  LAMD_HD_MEMBER kc_chunk *chunk(int c) const { return reinterpret_cast<kc_chunk *>(base + ((size_t)c * stride + lane) * 4); }
+  LAMD_HD_MEMBER fe load(int s) const {
+    const kc_chunk a = *chunk(3 * s), b = *chunk(3 * s + 1);
+    fe r;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { r.n[i] = a.w[i]; r.n[4 + i] = b.w[i]; }
+    r.n[8] = chunk(3 * s + 2)->w[0];
+    FE_SETMAG(r, 1);
+    return r;
+  }
+  LAMD_HD_MEMBER void store(int s, const fe &a) const {
+    *chunk(3 * s) = kc_chunk{{a.n[0], a.n[1], a.n[2], a.n[3]}};
+    *chunk(3 * s + 1) = kc_chunk{{a.n[4], a.n[5], a.n[6], a.n[7]}};
+    *chunk(3 * s + 2) = kc_chunk{{a.n[8], 0, 0, 0}};
+  }
+  LAMD_HD_MEMBER kc_lanes after(int slots) const { return kc_lanes{base + (size_t)slots * KC_SLOT_CHUNKS * stride * 4, stride, lane}; }
+  LAMD_HD_MEMBER kc_lanes chain(int s) const { return kc_lanes{base, stride, lane + (size_t)s}; }
+  // parked coordinate k of a chain (2 gr: X of entry gr, 2 gr + 1: its Y) in the table's own word format
+  LAMD_HD_MEMBER void park(int k, const fe &a) const {
+    u32 w[4 * KC_PARK_CHUNKS] = {};
+    slot_store_fe(w, a);
+#pragma unroll
+    for (int c = 0; c < KC_PARK_CHUNKS; c++)
+      *chunk(KC_CHAIN_SLOTS * KC_SLOT_CHUNKS + k * KC_PARK_CHUNKS + c) = kc_chunk{{w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]}};
+  }
+  LAMD_HD_MEMBER fe unpark(int k) const {
+    u32 w[4 * KC_PARK_CHUNKS];
+#pragma unroll
+    for (int c = 0; c < KC_PARK_CHUNKS; c++) {
+      const kc_chunk v = *chunk(KC_CHAIN_SLOTS * KC_SLOT_CHUNKS + k * KC_PARK_CHUNKS + c);
+#pragma unroll
+      for (int i = 0; i < 4; i++) w[4 * c + i] = v.w[i];
+    }
+    return slot_load_fe(w);
+  }
+};
+
+template <int T, class K>
+LAMD_HD void kc_bases_at(const K &key, const ge &q) {
   constexpr int D = kc_spacing(T), NPT = 2 * T - 1;
-  u32 *tmp = scratch + kc_sub_off(T);  // point 2i = B_i, point 2i+1 = C_i; x | y | z | prefix
+  const K tmp = key.after(kc_key_slots(T));  // point 2i = B_i, point 2i+1 = C_i; slots x | y | z | prefix
   gej b = gej_from_ge(q);
 #pragma unroll 1
   for (int i = 0; i < NPT; i++) {
-    store_raw(tmp + i * 36 + 0, b.x);
-    store_raw(tmp + i * 36 + 9, b.y);
-    store_raw(tmp + i * 36 + 18, fe_norm_weak(b.z));
+    tmp.store(i * 4 + 0, b.x);
+    tmp.store(i * 4 + 1, b.y);
+    tmp.store(i * 4 + 2, fe_norm_weak(b.z));
     if (i == NPT - 1) break;
     const int nd = (i & 1) ? D - 1 : 1;
 #pragma unroll 1
@@ -501,48 +569,52 @@ LAMD_HD void kc_bases(u32 *scratch, const ge &q) {
   fe acc = fe_set_int(1);
 #pragma unroll 1
   for (int i = 0; i < NPT; i++) {
-    store_raw(tmp + i * 36 + 27, acc);
-    acc = fe_mul(acc, slot_load_raw(tmp + i * 36 + 18));
+    tmp.store(i * 4 + 3, acc);
+    acc = fe_mul(acc, tmp.load(i * 4 + 2));
   }
-  store_raw(scratch + KC_ZB, acc);
+  key.store(3, acc);
   fe suffix = fe_set_int(1);
 #pragma unroll 1
   for (int i = NPT - 1; i >= 0; i--) {
-    const fe ratio = fe_mul(suffix, slot_load_raw(tmp + i * 36 + 27));
-    suffix = fe_mul(suffix, slot_load_raw(tmp + i * 36 + 18));
+    const fe ratio = fe_mul(suffix, tmp.load(i * 4 + 3));
+    suffix = fe_mul(suffix, tmp.load(i * 4 + 2));
     const fe r2 = fe_sqr(ratio);
-    const fe x = fe_mul(slot_load_raw(tmp + i * 36 + 0), r2);
-    const fe y = fe_mul(slot_load_raw(tmp + i * 36 + 9), fe_mul(r2, ratio));
-    u32 *dst = (i & 1) ? scratch + KC_C + (i >> 1) * 18 : tmp + i * 36;
-    store_raw(dst + 0, x);
-    store_raw(dst + 9, y);
+    const fe x = fe_mul(tmp.load(i * 4 + 0), r2);
+    const fe y = fe_mul(tmp.load(i * 4 + 1), fe_mul(r2, ratio));
+    if (i & 1) {
+      key.store(4 + (i >> 1) * 2, x);
+      key.store(5 + (i >> 1) * 2, y);
+    } else {
+      tmp.store(i * 4 + 0, x);
+      tmp.store(i * 4 + 1, y);
+    }
   }
   gej p;
-  p.x = slot_load_raw(tmp + (NPT - 1) * 36 + 0);
-  p.y = slot_load_raw(tmp + (NPT - 1) * 36 + 9);
+  p.x = tmp.load((NPT - 1) * 4 + 0);
+  p.y = tmp.load((NPT - 1) * 4 + 1);
   p.z = fe_set_int(1);
   p.inf = false;
 #pragma unroll 1
   for (int i = 0; i < T - 1; i++) {
     ge m;
-    m.x = slot_load_raw(tmp + 2 * i * 36 + 0);
-    m.y = fe_norm_weak(fe_neg(slot_load_raw(tmp + 2 * i * 36 + 9), 1));
+    m.x = tmp.load(2 * i * 4 + 0);
+    m.y = fe_norm_weak(fe_neg(tmp.load(2 * i * 4 + 1), 1));
     bool degenerate;
     fe h, rr;
     p = gej_add_ge_core(p, m, &degenerate, &h, &rr);
   }
-  store_raw(scratch + KC_P0 + 0, p.x);
-  store_raw(scratch + KC_P0 + 9, p.y);
-  store_raw(scratch + KC_P0 + 18, fe_norm_weak(p.z));
+  key.store(0, p.x);
+  key.store(1, p.y);
+  key.store(2, fe_norm_weak(p.z));
 }
-template <int T>
-LAMD_HD void kc_chain_fwd(u32 *tab, u32 *scratch, int sub) {
-  u32 *sp = scratch + kc_sub_off(T) + sub * KC_SUB_WORDS;
+// (sp: the view of THIS chain)
+template <int T, class K, class C>
+LAMD_HD void kc_chain_fwd_at(u32 *tab, const K &key, const C &sp, int sub) {
   u32 *ent = tab + sub * KC_SUB * SLOT_ENTRY_WORDS;
   gej p;
-  p.x = slot_load_raw(scratch + KC_P0 + 0);
-  p.y = slot_load_raw(scratch + KC_P0 + 9);
-  p.z = slot_load_raw(scratch + KC_P0 + 18);
+  p.x = key.load(0);
+  p.y = key.load(1);
+  p.z = key.load(2);
   p.inf = false;
   bool degenerate;
   fe h, rr;
@@ -550,46 +622,56 @@ LAMD_HD void kc_chain_fwd(u32 *tab, u32 *scratch, int sub) {
   for (int b = 0; b < T - 1 - KC_SUB_LOG; b++) {  // the chain's fixed high teeth
     if ((sub >> b) & 1) {
       ge c;
-      c.x = slot_load_raw(scratch + KC_C + (KC_SUB_LOG + b) * 18 + 0);
-      c.y = slot_load_raw(scratch + KC_C + (KC_SUB_LOG + b) * 18 + 9);
+      c.x = key.load(4 + (KC_SUB_LOG + b) * 2);
+      c.y = key.load(5 + (KC_SUB_LOG + b) * 2);
       p = gej_add_ge_core(p, c, &degenerate, &h, &rr);
       p.z = fe_norm_weak(p.z);
     }
   }
-  slot_store_fe(ent + 0, p.x);
-  slot_store_fe(ent + ENT_Y, p.y);
+  if constexpr (C::parks) {
+    sp.park(0, p.x);
+    sp.park(1, p.y);
+  } else {
+    slot_store_fe(ent + 0, p.x);
+    slot_store_fe(ent + ENT_Y, p.y);
+  }
 #pragma unroll 1
   for (int g = 1; g < KC_SUB; g++) {
     const int c = __builtin_ctz((unsigned)g), gr = g ^ (g >> 1);
     ge pt;
-    pt.x = slot_load_raw(scratch + KC_C + c * 18 + 0);
-    pt.y = slot_load_raw(scratch + KC_C + c * 18 + 9);
+    pt.x = key.load(4 + c * 2);
+    pt.y = key.load(5 + c * 2);
     pt = ge_neg_if(pt, ((gr >> c) & 1) == 0);  // tooth c goes - to +: add 2*B_c; + to -: subtract it
     p = gej_add_ge_core(p, pt, &degenerate, &h, &rr);
-    slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + 0, p.x);
-    slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + ENT_Y, p.y);
-    store_raw(sp + 18 + (g - 1) * 9, h);
+    if constexpr (C::parks) {
+      sp.park(2 * gr, p.x);
+      sp.park(2 * gr + 1, p.y);
+    } else {
+      slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + 0, p.x);
+      slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + ENT_Y, p.y);
+    }
+    sp.store(1 + g, h);
   }
-  store_raw(sp + 0, fe_norm_weak(p.z));
+  sp.store(0, fe_norm_weak(p.z));
 }
-template <int T>
-LAMD_HD void kc_prefix(u32 *tab, u32 *scratch, const ge &q) {
+// (sp: the view of the key's chain 0)
+template <int T, class K, class C>
+LAMD_HD void kc_prefix_at(u32 *tab, const K &key, const C &sp, const ge &q) {
   constexpr int NS = kc_nsub(T), NE = kc_ne(T);
-  u32 *sp = scratch + kc_sub_off(T);
   fe acc = fe_set_int(1);
 #pragma unroll 1
   for (int s = 0; s < NS; s++) {
-    store_raw(sp + s * KC_SUB_WORDS + 9, acc);
-    acc = fe_mul(acc, slot_load_raw(sp + s * KC_SUB_WORDS + 0));
+    sp.chain(s).store(1, acc);
+    acc = fe_mul(acc, sp.chain(s).load(0));
   }
-  const fe zc = fe_mul(acc, slot_load_raw(scratch + KC_ZB));
+  const fe zc = fe_mul(acc, key.load(3));
   slot_store_fe(tab + kc_words(T), zc);
   fe suffix = fe_set_int(1);
 #pragma unroll 1
   for (int s = NS - 1; s >= 0; s--) {
-    const fe ratio = fe_mul(suffix, slot_load_raw(sp + s * KC_SUB_WORDS + 9));
-    suffix = fe_mul(suffix, slot_load_raw(sp + s * KC_SUB_WORDS + 0));
-    store_raw(sp + s * KC_SUB_WORDS + 9, ratio);
+    const fe ratio = fe_mul(suffix, sp.chain(s).load(1));
+    suffix = fe_mul(suffix, sp.chain(s).load(0));
+    sp.chain(s).store(1, ratio);
   }
   const u32 betaw[8] = LAMD_BETA;
   const fe z2 = fe_sqr(zc);
@@ -599,24 +681,35 @@ LAMD_HD void kc_prefix(u32 *tab, u32 *scratch, const ge &q) {
   slot_store_fe(e + ENT_BX, fe_mul(x, fe_from_words(betaw)));
   slot_store_fe(e + ENT_Y, fe_mul(q.y, fe_mul(z2, zc)));
 }
-template <int T>
-LAMD_HD void kc_chain_bwd(u32 *tab, const u32 *scratch, int sub) {
+// (sp: the view of THIS chain)
+template <int T, class C>
+LAMD_HD void kc_chain_bwd_at(u32 *tab, const C &sp, int sub) {
   const u32 betaw[8] = LAMD_BETA;
   const fe beta = fe_from_words(betaw);
-  const u32 *sp = scratch + kc_sub_off(T) + sub * KC_SUB_WORDS;
   u32 *ent = tab + sub * KC_SUB * SLOT_ENTRY_WORDS;
-  fe rho = slot_load_raw(sp + 9);  // Zc / (Zb * Z_chain): the last entry's ratio
+  fe rho = sp.load(1);  // Zc / (Zb * Z_chain): the last entry's ratio
 #pragma unroll 1
   for (int g = KC_SUB - 1; g >= 0; g--) {  // rho = Zc / (Zb * Z_entry(g)): entry g+1 = entry g +- C had Z_(g+1) = Z_g * H_(g+1)
-    if (g != KC_SUB - 1) rho = fe_mul(rho, slot_load_raw(sp + 18 + g * 9));
+    if (g != KC_SUB - 1) rho = fe_mul(rho, sp.load(2 + g));
     const int gr = g ^ (g >> 1);
     const fe r2 = fe_sqr(rho);
-    const fe x = fe_mul(slot_load_fe(ent + gr * SLOT_ENTRY_WORDS + 0), r2);
-    const fe y = fe_mul(slot_load_fe(ent + gr * SLOT_ENTRY_WORDS + ENT_Y), fe_mul(r2, rho));
+    const fe x = fe_mul(C::parks ? sp.unpark(2 * gr) : slot_load_fe(ent + gr * SLOT_ENTRY_WORDS + 0), r2);
+    const fe y = fe_mul(C::parks ? sp.unpark(2 * gr + 1) : slot_load_fe(ent + gr * SLOT_ENTRY_WORDS + ENT_Y), fe_mul(r2, rho));
     slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + 0, x);
     slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + ENT_BX, fe_mul(x, beta));
     slot_store_fe(ent + gr * SLOT_ENTRY_WORDS + ENT_Y, y);
   }
+}
+// the stages on a key's flat scratch area
+template <int T>
+LAMD_HD void kc_bases(u32 *scratch, const ge &q) { kc_bases_at<T>(kc_flat{scratch}, q); }
+template <int T>
+LAMD_HD void kc_chain_fwd(u32 *tab, u32 *scratch, int sub) { kc_chain_fwd_at<T>(tab, kc_flat{scratch}, kc_flat{scratch + kc_sub_off(T)}.chain(sub), sub); }
+template <int T>
+LAMD_HD void kc_prefix(u32 *tab, u32 *scratch, const ge &q) { kc_prefix_at<T>(tab, kc_flat{scratch}, kc_flat{scratch + kc_sub_off(T)}, q); }
+template <int T>
+LAMD_HD void kc_chain_bwd(u32 *tab, const u32 *scratch, int sub) {
+  kc_chain_bwd_at<T>(tab, kc_flat{const_cast<u32 *>(scratch) + kc_sub_off(T)}.chain(sub), sub);
 }
 // sequential composition (CPU test harness; the engine launches the stages as separate kernels)
 template <int T>
