@@ -15,7 +15,13 @@
  * Verdict convention: ok[i] = 1 iff the reference would have accepted, i.e.
  *     parse_ok(signature) && parse_ok(key) && verify_ok
  * so a host-side parse failure and a device-side reject are indistinguishable from the
- * reference's combined outcome.  There is NO CPU fallback: without a working HIP device every
+ * reference's combined outcome.  Every byte the library writes into an `ok` buffer, on the host or on
+ * the device, is exactly 0 or 1 once the call's work is complete (for the *_device entry points: once
+ * the stream has reached the end of the call).  The kernels of one call hand rows to each other through
+ * markers in that byte -- 2: x(R) = r or the recovered point found, parity / compression still to be
+ * decided; 3: the bare formulas met Z = 0, the complete ones decide -- but those are internal and never
+ * leave the lane's workspace.  Callers may therefore test `if (!ok[i])`; a byte above 1 is a bug in the
+ * library, never an accept.  There is NO CPU fallback: without a working HIP device every
  * call returns LAMD_ERR_NO_DEVICE / LAMD_ERR_HIP and the caller must fail closed.
  *
  * Threading: a context owns one device, one stream and its staging buffers; calls on one

@@ -14,6 +14,16 @@ class LamdError(RuntimeError):
     pass
 
 
+def _verdicts(ok):
+    """the verdict column of a finished call -> bool.  Every byte the library writes is 0 or 1 (include/lightning_amd.h); the kernels' own
+    markers (2: BIP-340 parity or recovery still pending, 3: suspect, for the careful kernel) never leave a lane's workspace, and any
+    non-zero byte would read as an accept -- so anything else is an error, not a verdict."""
+    if ok.size and ok.max() > 1:
+        bad = np.flatnonzero(ok > 1)
+        raise LamdError("verdict byte %d at row %d is neither 0 nor 1 (%d such rows of %d)" % (int(ok[bad[0]]), int(bad[0]), bad.size, ok.size))
+    return ok.astype(bool)
+
+
 def _u8(a, shape_tail):
     a = np.ascontiguousarray(a, dtype=np.uint8)
     if a.ndim == 1:
@@ -255,7 +265,7 @@ class Engine:
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_verify_ecdsa_batch(self._ctx, n, hash32.ctypes.data, sig64.ctypes.data, pub.ctypes.data,
                                                     pub.shape[1], pub.shape[1], ok.ctypes.data))
-        return ok.astype(bool)
+        return _verdicts(ok)
 
     def verify_schnorr(self, msg32, xonly32, sig64):
         msg32, xonly32, sig64 = _u8(msg32, 32), _u8(xonly32, 32), _u8(sig64, 64)
@@ -265,7 +275,7 @@ class Engine:
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_verify_schnorr_batch(self._ctx, n, msg32.ctypes.data, xonly32.ctypes.data, sig64.ctypes.data,
                                                       ok.ctypes.data))
-        return ok.astype(bool)
+        return _verdicts(ok)
 
     def check_tx_sig_batch(self, preimages, sighash_types, has_witness, sig64, pub, key_layout=None):
         """preimages: list of bytes (BIP143 preimages); returns bool verdicts (gate + SHA256d + verify, all on the device).
@@ -281,7 +291,7 @@ class Engine:
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_check_tx_sig_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, types.ctypes.data, wit.ctypes.data,
                                                     sig64.ctypes.data, pub.ctypes.data, publen, pubstride, ok.ctypes.data))
-        return ok.astype(bool)
+        return _verdicts(ok)
 
     def check_tx_sig_tx_batch(self, txs, sig64, pub, key_layout=None):
         """txs: list of dicts {version, locktime, inputs: [(txid32, vout, sequence)], outputs: [(amount, spk)], input_num, amount, script,
@@ -310,7 +320,7 @@ class Engine:
                                                        amt.ctypes.data, ob.ctypes.data, out_off.ctypes.data, nout.ctypes.data, sb.ctypes.data,
                                                        sc_off.ctypes.data, types.ctypes.data, wit.ctypes.data, sig64.ctypes.data, pub.ctypes.data,
                                                        publen, pubstride, ok.ctypes.data))
-        return ok.astype(bool)
+        return _verdicts(ok)
 
     def commitment_call(self, commit_tx, remote_funding33, commit_sig64, commit_sighash_type, htlc_txs, remote_htlckey33, htlc_sigs64, htlc_sighash_types):
         """the arguments of check_commitment_signed() marshalled ONCE; returns a function that makes the C call and nothing else -> (first_bad, ok_rows).
@@ -339,7 +349,7 @@ class Engine:
         def call():
             self._chk(self._lib.lamd_check_commitment_signed(self._ctx, ctypes.addressof(ct), fk, cs, commit_sighash_type, n, ctypes.addressof(arr), hk,
                                                              sigs.ctypes.data, types.ctypes.data, ctypes.byref(first_bad), ok.ctypes.data))
-            return int(first_bad.value), ok.astype(bool)
+            return int(first_bad.value), _verdicts(ok)
         call.keep = keep
         return call
 
@@ -365,7 +375,7 @@ class Engine:
         ok = np.zeros(len(streams), dtype=np.uint8)
         self._chk(self._lib.lamd_bolt12_check_signature_batch(self._ctx, len(streams), blob.ctypes.data, off.ctypes.data, messagename, fieldname,
                                                               key33.ctypes.data, stride, sig64.ctypes.data, ok.ctypes.data))
-        return ok.astype(bool)
+        return _verdicts(ok)
 
     def bolt12_merkle_batch(self, streams, messagename, fieldname):
         """-> (merkle roots uint8 [n,32], signature hashes uint8 [n,32], ok bool [n])"""
@@ -374,7 +384,7 @@ class Engine:
         mk, sh, ok = np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_bolt12_merkle_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, messagename, fieldname, mk.ctypes.data,
                                                      sh.ctypes.data, ok.ctypes.data))
-        return mk, sh, ok.astype(bool)
+        return mk, sh, _verdicts(ok)
 
     def ecdsa_recover(self, hash32, sig64, recid):
         """numpy uint8 [n,32], [n,64], [n] -> (keys uint8 [n,33], ok bool [n]); secp256k1_ecdsa_recover semantics"""
@@ -386,7 +396,7 @@ class Engine:
         if n:
             self._chk(self._lib.lamd_ecdsa_recover_batch(self._ctx, n, hash32.ctypes.data, sig64.ctypes.data, recid.ctypes.data,
                                                          keys.ctypes.data, ok.ctypes.data))
-        return keys, ok.astype(bool)
+        return keys, _verdicts(ok)
 
     def bolt11_check(self, strings):
         """strings: BOLT #11 invoices as bolt11_decode() takes them (str or bytes, no "lightning:" prefix) -> (status int8 [n] (LAMD_B11_*),
@@ -397,7 +407,7 @@ class Engine:
         status, node, h, hn = np.zeros(n, dtype=np.int8), np.zeros((n, 33), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_bolt11_check_batch(self._ctx, n, blob.ctypes.data, off.ctypes.data, status.ctypes.data, node.ctypes.data, h.ctypes.data,
                                                     hn.ctypes.data))
-        return status, node, h, hn.astype(bool)
+        return status, node, h, _verdicts(hn)
 
     def checkmessage(self, messages, zbases):
         """messages, zbases: the message and the zbase32 signature string of each checkmessage call (str or bytes) -> (status int8 [n] (LAMD_MSG_*),
@@ -458,7 +468,7 @@ class Engine:
         out = np.zeros((n, 64), dtype=np.uint8)
         ok = np.zeros(n, dtype=np.uint8)
         self._chk(self._lib.lamd_pubkey_parse_batch(self._ctx, n, pub.ctypes.data, ln, ln, out.ctypes.data, ok.ctypes.data))
-        return out, ok.astype(bool)
+        return out, _verdicts(ok)
 
     def sigcheck_gossip(self, msgs, node_ids=None):
         """msgs: list of bytes (raw wire messages).  node_ids: list of 33-byte ids (or None entries), needed for
@@ -931,13 +941,13 @@ class Engine:
         ok = np.zeros(cap, dtype=np.uint8)
         n = ctypes.c_size_t(0)
         self._chk(self._lib.lamd_wait(self._ctx, ok.ctypes.data, cap, ctypes.byref(n)))
-        return ok[:n.value].astype(bool)
+        return _verdicts(ok[:n.value])
 
     def poll(self, cap=1 << 20):
         ok = np.zeros(cap, dtype=np.uint8)
         n = ctypes.c_size_t(0)
         rc = self._chk(self._lib.lamd_poll(self._ctx, ok.ctypes.data, cap, ctypes.byref(n)))
-        return ok[:n.value].astype(bool) if rc == 1 else None
+        return _verdicts(ok[:n.value]) if rc == 1 else None
 
     # ---- device-resident API (torch uint8 CUDA tensors; asynchronous on self.stream_ptr)
     def verify_ecdsa_device(self, d_hash, d_sig, d_pub, d_ok):

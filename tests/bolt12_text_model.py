@@ -377,6 +377,18 @@ def synth(seed=12):
         raw(hrp, stream_of(swap(fields, 240, bytes(64))), BAD_SIGNATURE, "range/%s-zero-signature" % tag)
         raw(hrp, stream_of(sorted(fields + [(241, b"second")])), OK, "sig/%s-241-beside-240" % tag)
         raw(hrp, stream_of(sorted(fields + [(1000, b"")])), OK, "sig/%s-1000-beside-240" % tag)
+    # -- signatures over the invoice's own sighash that only the last steps of the BIP-340 test refuse (bip340_stage2.py): R = s*G - e*P has x(R) = r
+    #    and an ODD y (the nonce is not negated); R is the point at infinity (s = e*d).  d is the key with even y (pub starts 02)
+    body = sorted(f for f in invoice_f if f[0] != 240)
+    h = R.bolt12_sighash(MESSAGENAME[KIND_INVOICE], b"signature", R.bolt12_merkle(body))
+    k = int.from_bytes(R.sha256(b"odd_R" + h), "big") % R.N
+    Rk = R.pmul(k, R.G)
+    k = k if Rk[1] & 1 else R.N - k
+    rx = Rk[0].to_bytes(32, "big")
+    e = int.from_bytes(R.tagged_hash("BIP0340/challenge", rx + pub[1:] + h), "big") % R.N
+    raw("lni", stream_of(sorted(body + [(240, rx + ((k + e * d) % R.N).to_bytes(32, "big"))])), BAD_SIGNATURE, "stage2/invoice-odd-R")
+    raw("lni", stream_of(sorted(body + [(240, rx + ((R.N - k + e * d) % R.N).to_bytes(32, "big"))])), OK, "stage2/invoice-even-R-twin")
+    raw("lni", stream_of(sorted(body + [(240, rx + (e * d % R.N).to_bytes(32, "big"))])), BAD_SIGNATURE, "stage2/invoice-R-inf")
     raw("lnr", stream_of(invoice_f), OUT_OF_RANGE, "kind/invoice-data-under-lnr")
     raw("lni", stream_of(invreq_f), NO_KEY, "kind/invreq-data-under-lni")
     raw("lno", stream_of(invreq_f), OUT_OF_RANGE, "kind/invreq-data-under-lno")

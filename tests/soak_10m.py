@@ -12,6 +12,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import numpy as np
 import orc
+from verdict_bytes import strict_bool
 from lightning_amd import Engine, workload
 
 
@@ -43,10 +44,10 @@ def run(eng=None):
 
     w = workload.make_ecdsa(eng, 1_000_000, publen=65)
     eng.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok); eng.synchronize()
-    rec("configs[1] 1M ECDSA-65", w.d_ok.cpu().numpy().astype(bool), orc.ecdsa_verify_batch(w.cols[0], w.cols[1], w.cols[2], 65, cores).astype(bool), w.expect)
+    rec("configs[1] 1M ECDSA-65", strict_bool(w.d_ok.cpu().numpy()), orc.ecdsa_verify_batch(w.cols[0], w.cols[1], w.cols[2], 65, cores).astype(bool), w.expect)
     w = workload.make_schnorr(eng, 1_000_000)
     eng.verify_schnorr_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok); eng.synchronize()
-    rec("configs[2] 1M BIP-340", w.d_ok.cpu().numpy().astype(bool), orc.schnorr_verify_batch(w.cols[0], w.cols[1], w.cols[2], cores).astype(bool), w.expect)
+    rec("configs[2] 1M BIP-340", strict_bool(w.d_ok.cpu().numpy()), orc.schnorr_verify_batch(w.cols[0], w.cols[1], w.cols[2], cores).astype(bool), w.expect)
     g = workload.make_gossip(eng, 500_000, 2_000_000)
     eng.sigcheck_gossip_device(g.n, g.d_msgs, g.d_off, g.d_ids, g.d_rowbase, g.rows, g.d_verdict); eng.synchronize()
     gv = g.d_verdict.cpu().numpy()
@@ -60,8 +61,8 @@ def run(eng=None):
     we, ws = st["ecdsa"], st["schnorr"]
     eng.verify_ecdsa_device(we.dev[0], we.dev[1], we.dev[2], we.d_ok)
     eng.verify_schnorr_device(ws.dev[0], ws.dev[1], ws.dev[2], ws.d_ok); eng.synchronize()
-    rec("configs[4] commit storm ECDSA part", we.d_ok.cpu().numpy().astype(bool), orc.ecdsa_verify_batch(we.cols[0], we.cols[1], we.cols[2], 33, cores).astype(bool), we.expect)
-    rec("configs[4] commit storm BIP-340 part", ws.d_ok.cpu().numpy().astype(bool), orc.schnorr_verify_batch(ws.cols[0], ws.cols[1], ws.cols[2], cores).astype(bool), ws.expect)
+    rec("configs[4] commit storm ECDSA part", strict_bool(we.d_ok.cpu().numpy()), orc.ecdsa_verify_batch(we.cols[0], we.cols[1], we.cols[2], 33, cores).astype(bool), we.expect)
+    rec("configs[4] commit storm BIP-340 part", strict_bool(ws.d_ok.cpu().numpy()), orc.schnorr_verify_batch(ws.cols[0], ws.cols[1], ws.cols[2], cores).astype(bool), ws.expect)
     out["total_verifies"] = total
     out["total_mismatches"] = mism
     out["wall_s"] = time.time() - t00

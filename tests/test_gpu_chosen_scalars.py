@@ -19,6 +19,7 @@ import torch
 
 import chosen_scalars as cs
 import pyref
+from verdict_bytes import strict_bool
 
 pytestmark = pytest.mark.gpu
 BITS = 24                            # verify_core.h GTABLE_WINDOW_BITS as shipped
@@ -45,7 +46,7 @@ def _on_device(e, cols):
     torch.cuda.synchronize()
     e.verify_ecdsa_device(dev[0], dev[1], dev[2], d_ok)
     e.synchronize()
-    return d_ok.cpu().numpy().astype(bool)
+    return strict_bool(d_ok.cpu().numpy())
 
 
 def _cols_exp(orc, rows, publen):

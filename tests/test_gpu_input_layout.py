@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gossip_stream as gs  # noqa: E402
 import pyref  # noqa: E402
+from verdict_bytes import strict_bool  # noqa: E402
 
 H = bytes.fromhex
 N, P = pyref.N, pyref.P
@@ -595,7 +596,7 @@ def test_strided_keys_pubkey_parse(eng, kat, orc):
     for stride in (32, 33, 40):
         for fill in FILLS if stride > 32 else ("ff",):
             out, ok = _parse(eng, strided_column(xs, stride, fill, np.nonzero(signed_rows(32)[3] != 2)[0]) if stride > 32 else xs, len(xs), 32, stride)
-            assert [bool(k) for k in ok] == [w is not None for w in want], (stride, fill)
+            assert strict_bool(ok).tolist() == [w is not None for w in want], (stride, fill)
             assert all(o.tobytes() == w for o, w in zip(out, want) if w is not None), (stride, fill)
 
 

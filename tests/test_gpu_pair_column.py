@@ -10,6 +10,7 @@ import torch
 
 import chosen_scalars as cs
 import pyref
+from verdict_bytes import strict_bool
 
 pytestmark = pytest.mark.gpu
 N = pyref.N
@@ -46,7 +47,7 @@ def _on_device(e, mode, cols):
     torch.cuda.synchronize()
     (e.verify_ecdsa_device if mode == "ecdsa" else e.verify_schnorr_device)(dev[0], dev[1], dev[2], d_ok)
     e.synchronize()
-    return d_ok.cpu().numpy().astype(bool)
+    return strict_bool(d_ok.cpu().numpy())
 
 
 def _ecdsa65(orc, rnd, keys):

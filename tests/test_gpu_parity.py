@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import pyref
+from verdict_bytes import strict_bool
 
 pytestmark = pytest.mark.gpu
 H = bytes.fromhex
@@ -202,7 +203,7 @@ def test_device_generator_round_trip_and_oracle_sample(eng, orc):
         w = workload.make_ecdsa(eng, 20000, nkeys=257, publen=publen)
         eng.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
         eng.synchronize()
-        got = w.d_ok.cpu().numpy().astype(bool)
+        got = strict_bool(w.d_ok.cpu().numpy())
         assert np.array_equal(got, w.expect), (publen, np.nonzero(got != w.expect)[0][:10], w.classes[got != w.expect][:10])
         assert (~w.expect).sum() == 2000
         sl = slice(0, 1500)
@@ -212,7 +213,7 @@ def test_device_generator_round_trip_and_oracle_sample(eng, orc):
     w = workload.make_schnorr(eng, 20000, nkeys=300)
     eng.verify_schnorr_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
     eng.synchronize()
-    got = w.d_ok.cpu().numpy().astype(bool)
+    got = strict_bool(w.d_ok.cpu().numpy())
     assert np.array_equal(got, w.expect), (np.nonzero(got != w.expect)[0][:10], w.classes[got != w.expect][:10])
     sl = slice(0, 1500)
     exp = orc.schnorr_verify_batch(np.ascontiguousarray(w.cols[0][sl]), np.ascontiguousarray(w.cols[1][sl]),
@@ -368,8 +369,8 @@ def test_cfg5_full_size_properties(eng, orc):
     eng.verify_ecdsa_device(we.dev[0], we.dev[1], we.dev[2], we.d_ok)
     eng.verify_schnorr_device(ws.dev[0], ws.dev[1], ws.dev[2], ws.d_ok)
     eng.synchronize()
-    assert np.array_equal(we.d_ok.cpu().numpy().astype(bool), we.expect)
-    assert np.array_equal(ws.d_ok.cpu().numpy().astype(bool), ws.expect)
+    assert np.array_equal(strict_bool(we.d_ok.cpu().numpy()), we.expect)
+    assert np.array_equal(strict_bool(ws.d_ok.cpu().numpy()), ws.expect)
     assert (~we.expect).sum() + (~ws.expect).sum() == int(we.n * 0.001) + int(ws.n * 0.001)
     ce = orc.ecdsa_verify_batch(we.cols[0], we.cols[1], we.cols[2], we.cols[2].shape[1], _cores()).astype(bool)
     cs = orc.schnorr_verify_batch(ws.cols[0], ws.cols[1], ws.cols[2], _cores()).astype(bool)
@@ -435,7 +436,7 @@ def test_keyed_path_auto_selection_and_parity(eng, orc):
     inf = eng.info()
     assert inf["last_keyed"] == 10 and 100 <= inf["last_unique_keys"] < 600  # >= 48 signatures per key: the 10-tooth comb
     assert inf["last_cache_hits"] == 0 and 90 <= inf["last_new_tables"] <= 110
-    got = w.d_ok.cpu().numpy().astype(bool)
+    got = strict_bool(w.d_ok.cpu().numpy())
     assert np.array_equal(got, w.expect), (np.nonzero(got != w.expect)[0][:10], w.classes[got != w.expect][:10])
     sl = slice(0, 1200)
     exp = orc.ecdsa_verify_batch(np.ascontiguousarray(w.cols[0][sl]), np.ascontiguousarray(w.cols[1][sl]), np.ascontiguousarray(w.cols[2][sl]), 33, 4)
@@ -444,14 +445,14 @@ def test_keyed_path_auto_selection_and_parity(eng, orc):
     eng.verify_schnorr_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
     eng.synchronize()
     assert eng.info()["last_keyed"] == 7                                       # ~13 signatures per key: the 7-tooth comb
-    got = w.d_ok.cpu().numpy().astype(bool)
+    got = strict_bool(w.d_ok.cpu().numpy())
     assert np.array_equal(got, w.expect), (np.nonzero(got != w.expect)[0][:10], w.classes[got != w.expect][:10])
     w = workload.make_ecdsa(eng, 30000, nkeys=1 << 40, publen=65)          # all keys distinct
     eng.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
     eng.synchronize()
     inf = eng.info()
     assert not inf["last_keyed"] and inf["last_unique_keys"] > 29000
-    assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect)
+    assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect)
 
 
 def test_chunk_splitting_small_chunks(orc, kat):
@@ -467,7 +468,7 @@ def test_chunk_splitting_small_chunks(orc, kat):
         w = workload.make_ecdsa(e, 5300, nkeys=40, publen=33)
         e.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
         e.synchronize()
-        assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect)
+        assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect)
         assert np.array_equal(e.verify_ecdsa(w.cols[0], w.cols[1], w.cols[2]), w.expect)
         ws = workload.make_schnorr(e, 3100, nkeys=1 << 40)
         assert np.array_equal(e.verify_schnorr(ws.cols[0], ws.cols[1], ws.cols[2]), ws.expect)
@@ -570,7 +571,7 @@ def test_lanes_back_to_back_calls_without_host_sync(eng, orc):
         eng.synchronize()
         gv = g.d_verdict
         for kind, w in ws:
-            assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect), (rep, kind, w.n)
+            assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect), (rep, kind, w.n)
         assert np.array_equal(gv.cpu().numpy(), g.expect)
     inf = [eng.info(k) for k in range(eng.info()["lanes"])]
     assert len(inf) == 6 and {i["last_mode"] for i in inf} <= {0, 1}   # (LAMD_LANES default)
@@ -582,7 +583,7 @@ def test_lanes_back_to_back_calls_without_host_sync(eng, orc):
     eng.stream_wait_results(torch.cuda.current_stream().cuda_stream)
     got = w.d_ok.clone()                       # on torch's stream: ordered after the verification by the event
     torch.cuda.synchronize()
-    assert np.array_equal(got.cpu().numpy().astype(bool), w.expect)
+    assert np.array_equal(strict_bool(got.cpu().numpy()), w.expect)
     eng.synchronize()
 
 
@@ -620,7 +621,7 @@ def test_two_phase_join_and_event_ordering(eng):
     consumer.synchronize()
     eng.synchronize()
     for w, got in copies:
-        assert np.array_equal(got.cpu().numpy().astype(bool), w.expect), w.kind
+        assert np.array_equal(strict_bool(got.cpu().numpy()), w.expect), w.kind
 
 
 def test_single_lane_mode_matches(orc):
@@ -637,8 +638,8 @@ def test_single_lane_mode_matches(orc):
         e.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
         e.verify_schnorr_device(s.dev[0], s.dev[1], s.dev[2], s.d_ok)
         e.synchronize()
-        assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect)
-        assert np.array_equal(s.d_ok.cpu().numpy().astype(bool), s.expect)
+        assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect)
+        assert np.array_equal(strict_bool(s.d_ok.cpu().numpy()), s.expect)
         assert e.info()["lanes"] == 1 and e.info(0) == e.info()
         with pytest.raises(LamdError):
             e.info(1)
@@ -686,7 +687,7 @@ def test_scheduling_variants_give_the_same_verdicts(orc, env):
             e.verify_ecdsa_device(x.dev[0], x.dev[1], x.dev[2], x.d_ok)
             e.synchronize()
             for wl in (w, s, x):
-                assert np.array_equal(wl.d_ok.cpu().numpy().astype(bool), wl.expect), (env, rep, wl.kind)
+                assert np.array_equal(strict_bool(wl.d_ok.cpu().numpy()), wl.expect), (env, rep, wl.kind)
         # lamd_set_chunk_rows at run time: the same calls cut in two / in many, then whole again
         for rows in (60000, 4096, 0):
             e.set_chunk_rows(rows)
@@ -700,8 +701,8 @@ def test_scheduling_variants_give_the_same_verdicts(orc, env):
             e.verify_ecdsa_device(x.dev[0], x.dev[1], x.dev[2], x.d_ok)
             e.synchronize()
             torch.cuda.synchronize()
-            assert np.array_equal(got_w.cpu().numpy().astype(bool), w.expect), (env, rows)
-            assert np.array_equal(x.d_ok.cpu().numpy().astype(bool), x.expect), (env, rows)
+            assert np.array_equal(strict_bool(got_w.cpu().numpy()), w.expect), (env, rows)
+            assert np.array_equal(strict_bool(x.d_ok.cpu().numpy()), x.expect), (env, rows)
         sample = slice(0, 3000)
         assert np.array_equal(orc.ecdsa_verify_batch(*[np.ascontiguousarray(c[sample]) for c in w.cols], 33, 4).astype(bool), w.expect[sample])
         assert np.array_equal(orc.schnorr_verify_batch(*[np.ascontiguousarray(c[sample]) for c in s.cols], 4).astype(bool), s.expect[sample])
@@ -766,7 +767,7 @@ def test_one_call_larger_than_a_chunk_full_size(eng):
     w = workload.make_ecdsa(eng, 5_000_000, seed=4242, nkeys=300_000, publen=33)
     eng.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
     eng.synchronize()
-    got = w.d_ok.cpu().numpy().astype(bool)
+    got = strict_bool(w.d_ok.cpu().numpy())
     assert np.array_equal(got, w.expect), np.nonzero(got != w.expect)[0][:10]
     assert 0 < (~w.expect).sum() < w.n
 
@@ -1177,8 +1178,8 @@ def test_key_table_cache_warm_cold_and_bounded(orc):
             e.verify_schnorr_device(s.dev[0], s.dev[1], s.dev[2], s.d_ok)
             e.synchronize()
             isch = e.info()
-            assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect), rep
-            assert np.array_equal(s.d_ok.cpu().numpy().astype(bool), s.expect), rep
+            assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect), rep
+            assert np.array_equal(strict_bool(s.d_ok.cpu().numpy()), s.expect), rep
             if rep == 0:
                 assert ie["last_cache_hits"] == 0 and ie["last_new_tables"] > 3500 and ie["last_keyed"] == 7
                 assert isch["last_new_tables"] >= 290 and isch["last_keyed"] == 10
@@ -1194,7 +1195,7 @@ def test_key_table_cache_warm_cold_and_bounded(orc):
         assert np.array_equal(got, s.expect[sel]) and e.info()["last_cache_hits"] == len(sel)
         # oracle pin on a sample of the cached-path verdicts
         exp = orc.ecdsa_verify_batch(w.cols[0][:1500], w.cols[1][:1500], w.cols[2][:1500], 33, 4).astype(bool)
-        assert np.array_equal(w.d_ok.cpu().numpy()[:1500].astype(bool), exp)
+        assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()[:1500]), exp)
         e.cache_clear()
         e.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
         e.synchronize()
@@ -1209,8 +1210,8 @@ def test_key_table_cache_warm_cold_and_bounded(orc):
                 e.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
                 e.verify_schnorr_device(s.dev[0], s.dev[1], s.dev[2], s.d_ok)
                 e.synchronize()
-                assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect), rep
-                assert np.array_equal(s.d_ok.cpu().numpy().astype(bool), s.expect), rep
+                assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect), rep
+                assert np.array_equal(strict_bool(s.d_ok.cpu().numpy()), s.expect), rep
             assert e.info()["cache_resets"] >= 1 and e.info()["cache_capacity"] == 640
     finally:
         del os.environ["LAMD_CACHE_KEYS"], os.environ["LAMD_CACHE_KEYS10"]
@@ -1221,7 +1222,7 @@ def test_key_table_cache_warm_cold_and_bounded(orc):
             for rep in range(2):
                 e.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
                 e.synchronize()
-                assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect)
+                assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect)
                 assert not e.info()["cache_enabled"] and e.info()["last_cache_hits"] == 0 and e.info()["last_new_tables"] > 2500
     finally:
         del os.environ["LAMD_CACHE"]
@@ -1560,7 +1561,7 @@ def test_one_launch_path_block_boundaries_and_mixed_shapes(orc):
                 for _ in range(2):                                                                    # second call: the host has seen the tables published
                     e.verify_ecdsa_device(w.dev[0], w.dev[1], w.dev[2], w.d_ok)
                     e.synchronize()
-                assert np.array_equal(w.d_ok.cpu().numpy().astype(bool), w.expect)
+                assert np.array_equal(strict_bool(w.d_ok.cpu().numpy()), w.expect)
             rng = np.random.default_rng(77 + publen)
             o = 0
             for n in (1, 63, 64, 65, 127, 128, 129, 1000, 4095, 4096, 4097):
@@ -1605,7 +1606,7 @@ def test_small_batches_with_a_cache_take_the_lookup_path(kat, orc):
         big = workload.make_ecdsa(e, 40000, seed=777, nkeys=600, publen=33)           # 66 rows per key: cached combs
         e.verify_ecdsa_device(big.dev[0], big.dev[1], big.dev[2], big.d_ok)
         e.synchronize()
-        assert np.array_equal(big.d_ok.cpu().numpy().astype(bool), big.expect) and e.info()["last_new_tables"] > 500
+        assert np.array_equal(strict_bool(big.d_ok.cpu().numpy()), big.expect) and e.info()["last_new_tables"] > 500
         e.verify_ecdsa_device(big.dev[0], big.dev[1], big.dev[2], big.d_ok)           # the host has now seen the publishing call complete
         e.synchronize()
         fresh = workload.make_ecdsa(e, 4000, seed=778, nkeys=1 << 40, publen=33, group=1)      # keys the cache has never seen, every row its own

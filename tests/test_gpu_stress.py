@@ -9,6 +9,8 @@ import random
 import numpy as np
 import pytest
 
+from verdict_bytes import strict_bool
+
 pytestmark = pytest.mark.gpu
 H = bytes.fromhex
 
@@ -166,5 +168,5 @@ def test_calls_in_flight_may_share_one_verdict_buffer(monkeypatch):
                 eng.verify_schnorr_device(ws.dev[0], ws.dev[1], ws.dev[2], ws.d_ok)
             eng.synchronize()
             torch.cuda.synchronize()
-            assert int((we.d_ok.cpu().numpy().astype(bool) != we.expect).sum()) == 0, rep
-            assert int((ws.d_ok.cpu().numpy().astype(bool) != ws.expect).sum()) == 0, rep
+            assert int((strict_bool(we.d_ok.cpu().numpy()) != we.expect).sum()) == 0, rep
+            assert int((strict_bool(ws.d_ok.cpu().numpy()) != ws.expect).sum()) == 0, rep

@@ -18,6 +18,7 @@ import torch
 import chosen_scalars as cs
 import pyref
 from test_gpu_tables import _check_table, _key_words
+from verdict_bytes import strict_bool
 
 pytestmark = pytest.mark.gpu
 
@@ -117,7 +118,7 @@ def _call(e, mat, mode, plan):
     torch.cuda.synchronize()
     (e.verify_ecdsa_device if mode == "ecdsa" else e.verify_schnorr_device)(dev[0], dev[1], dev[2], d_ok)
     e.synchronize()
-    return d_ok.cpu().numpy().astype(bool), np.array(exp, dtype=bool)
+    return strict_bool(d_ok.cpu().numpy()), np.array(exp, dtype=bool)
 
 
 def _check_tables(e, mat, mode, plan):
@@ -220,7 +221,7 @@ def test_suspect_rows_take_the_careful_pass(engines, orc, grid):
     torch.cuda.synchronize()
     e.verify_ecdsa_device(dev[0], dev[1], dev[2], d_ok)
     e.synchronize()
-    got = d_ok.cpu().numpy().astype(bool)
+    got = strict_bool(d_ok.cpu().numpy())
     assert np.array_equal(got, exp), [(rows[i].tag, hex(rows[i].u1), hex(rows[i].u2)) for i in np.nonzero(got != exp)[0][:10]]
     inf = e.info()
     assert inf["last_keyed"] in (7, 10) and inf["last_hot_rows"] == len(rows) and inf["last_suspect_rows"] >= len(u2s), inf

@@ -13,6 +13,7 @@ import pytest
 import pyref
 
 import gtable_cases as gc
+from verdict_bytes import strict_bool
 
 pytestmark = pytest.mark.gpu
 
@@ -307,7 +308,7 @@ def test_every_entry_of_every_key_table(engines, orc, T, tree, K):
         d_ok = torch.zeros(len(hs), dtype=torch.uint8, device="cuda")
         e.verify_ecdsa_device(d_h, d_s, d_p, d_ok)
         e.synchronize()
-        got = d_ok.cpu().numpy().astype(bool)
+        got = strict_bool(d_ok.cpu().numpy())
         exp = orc.ecdsa_verify_batch(hs, sg, pk, pk.shape[1], 4).astype(bool)
         assert np.array_equal(got, exp)
         assert list(exp) == [d is not None for d in ds] * 2                 # valid rows under every real key, none under the other
