@@ -930,6 +930,68 @@ int lamd_channel_update_receive_batch(lamd_ctx *ctx, const lamd_store_digest *di
 				      uint64_t *add_off, uint8_t *out, void *d_out, size_t out_cap, size_t edit_cap, uint32_t *del_rec,
 				      uint32_t *set_rec, uint32_t *set_ts, uint32_t *set_crc, lamd_update_receive_summary *summary);
 
+/* ---- receiving node_announcement batches against a store image on the device: the receive path of gossmap_manage_node_announcement() /
+ * process_node_announcement() (gossipd/gossmap_manage.c:1122-1248) for a drained queue of raw messages.  The directory holds what that path
+ * asks the gossmap: the distinct node ids ranked by memcmp, each node's announcement record in force, the ranks of every channel's two
+ * nodes, and the image itself.  The call parses the messages, runs ONE signature batch, each message under its own node_id, and applies
+ * "newer wins" in ARRIVAL ORDER; it returns a verdict per message and the exact bytes and edits gossip_store_add / _del
+ * (gossipd/gossip_store.c:49-78, 622-653) would make.  It changes neither the image nor the directory: apply the plan, then build them again.
+ * The directory must come from this context (LAMD_ERR_ARG otherwise).  Message i is msgs + off[i] .. off[i + 1].  announcements_pending
+ * (0 / 1): the caller's pending or too-early channel_announcement maps are not empty (:1225-1226).  There is no chain hash, no clock and no
+ * source peer: the reference applies none of them to this message (timestamp_reasonable() is not called on this path, the peer is only scored).
+ * STATUS per message: the first that applies, in the reference's order.
+ *   -1  malformed (:1186-1199): shorter than 142 bytes (2 + 64 + 2 + flen + 4 + 33 + 3 + 32 + 2 with flen = 0), longer than 65535, type not
+ *       257, flen or addrlen past the end, the bytes behind the addresses no valid node_ann_tlvs stream (fromwire_tlv's rules: strictly
+ *       ascending types, lengths inside the message, an unknown even type fails, an unknown odd one is skipped; type 1, option_will_fund, has 10
+ *       to 14 bytes and a minimal tu32), or signature r or s >= n (wire/fromwire.c:196-198)
+ *    1  malformed wireaddrs (:1202-1215, common/wireaddr.c:30-69, 858-889): `addresses` is walked descriptor by descriptor -- type 1: 4
+ *       bytes, 2: 16, 3: 10, 4: 35, 5: a length byte, then that many; each followed by a 2-byte port -- and a descriptor is cut off
+ *       somewhere, behind its type byte or a type 5's length byte included.  An unknown type ends the walk successfully, whatever follows;
+ *       port 0 is ignored, no error.
+ *    2  bad signature under the message's own node_id (:1217-1220).  An id that is no valid key fails here.
+ *    3  held: the node id is not in the directory and announcements_pending is set (:1225-1233).  The caller queues it.
+ *    4  unknown node (:1235-1243)
+ *    5  stale: ts < the timestamp in force of its node       (:1133-1140)
+ *    6  duplicate: ts == the timestamp in force
+ *    0  accepted
+ *   The timestamp in force of a node starts as the HEADER timestamp of its announcement record in the image (gossip_store_get_timestamp; the
+ *   directory's nann_rec) or, for a node without one, as "none" (anything that got this far is accepted), and then becomes the timestamp of
+ *   each accepted message in turn.
+ * FLAGS per message (0 unless stated; the bit values of lamd_channel_update_receive_batch):
+ *   bit 0  SUPERSEDED   accepted, and a later message of the batch was accepted for the same node: its record is added, then deleted
+ *   bit 2  DYING        accepted, and every channel of the node carries 0x0800 on its announcement record (all_node_channels_dying(),
+ *                       :288-298, :1145-1149)
+ * node[i]: the node's rank in the directory; UINT32_MAX for the statuses -1 and 1 .. 4.
+ * THE PLAN
+ *   add_msg[j], add_off[j], j < adds: one store record per accepted message, in arrival order, exactly as lamd_channel_update_receive_batch
+ *     writes them: be16 flags = 0x2000 | 0x0800 if DYING | 0x8000 if SUPERSEDED, be16 len, be32 crc32c seeded with ts, be32 ts, the message.
+ *   del_rec[k], k < deletions: the image records the nodes held before (each deleted by its node's first accepted message), ascending: set
+ *     their DELETED bit.
+ *   There are no re-stamps.
+ * SIZES  as lamd_channel_update_receive_batch: add_cap must hold the adds, edit_cap the deletions, out_cap the bytes (when out or d_out is
+ *   given).  One too small: LAMD_ERR_ARG with summary, status, flags and node filled in and nothing written to the plan's arrays, out or
+ *   d_out.  All caps 0: the verdicts and the sizes alone.  The bytes go to out (host), d_out (device, any alignment), or neither.
+ * Device work, on the context's stream: k_nr_alive (one lane per channel: a channel that is not dying stores a 1 for both of its nodes),
+ * k_nr_classify (one lane per message: byte loads at any alignment, statuses -1 and 1, the 33-byte bisection, the row's span; rows compacted
+ * with one atomic per wave -- an unknown node has a row too, the reference checks the signature first), ONE signature batch over the spans,
+ * k_nr_settle (statuses 2 .. 4), a stable rocPRIM radix sort of the candidates by rank, an inclusive max-scan over (rank << 33) | (ts + 1) --
+ * whatever the number of messages aimed at one node --, k_nr_resolve (seeded with the header timestamp read from the image; SUPERSEDED from
+ * the node's last row by bisection, DYING from k_nr_alive), a sort of the deleted records, two exclusive scans in arrival order, k_nr_plan, and
+ * behind the first wait the update call's k_rx_encode and k_rx_copy.  The host waits once for the verdicts and sizes and once for the lists
+ * and bytes.  Limits: n below 2^31, fewer than 2^30 nodes, off non-decreasing. */
+typedef struct {
+	uint64_t by_status[8];      /* messages: [0] .. [6] statuses 0 .. 6, [7] malformed */
+	uint64_t accepted, superseded;
+	uint64_t adds, bytes;       /* what add_cap and out_cap must hold */
+	uint64_t deletions;         /* what edit_cap must hold */
+	uint64_t signature_rows;    /* the rows of the signature batch */
+	double stage_ms[5];         /* with lamd_set_timing: classify, signatures, resolve, plan, encode */
+} lamd_node_receive_summary;
+int lamd_node_announcement_receive_batch(lamd_ctx *ctx, const lamd_store_directory *directory, size_t n, const uint8_t *msgs, const uint64_t *off,
+					 int announcements_pending, int8_t *status, uint8_t *flags, uint32_t *node, size_t add_cap,
+					 uint32_t *add_msg, uint64_t *add_off, uint8_t *out, void *d_out, size_t out_cap, size_t edit_cap,
+					 uint32_t *del_rec, lamd_node_receive_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

@@ -104,6 +104,12 @@ class LamdUpdateReceiveSummary(ctypes.Structure):
                 ("signature_rows", ctypes.c_uint64)]
 
 
+class LamdNodeReceiveSummary(ctypes.Structure):
+    """lamd_node_receive_summary (include/lightning_amd.h): what lamd_node_announcement_receive_batch reports about a batch of node_announcements"""
+    _fields_ = [("by_status", ctypes.c_uint64 * 8), ("accepted", ctypes.c_uint64), ("superseded", ctypes.c_uint64), ("adds", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("deletions", ctypes.c_uint64), ("signature_rows", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 5)]
+
+
 class LamdGtableAuditResult(ctypes.Structure):
     """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
     _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
@@ -187,6 +193,8 @@ SYMBOLS = {
     "lamd_channel_update_receive_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint32, c_u8p, c_sz, c_u8p, c_u8p,
                                                          c_u8p, c_sz, c_sz, c_u8p, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, ctypes.c_void_p, c_sz, c_sz, c_u8p,
                                                          c_u8p, c_u8p, c_u8p, ctypes.POINTER(LamdUpdateReceiveSummary)]),
+    "lamd_node_announcement_receive_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.c_int, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
+                                                            c_u8p, ctypes.c_void_p, c_sz, c_sz, c_u8p, ctypes.POINTER(LamdNodeReceiveSummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

@@ -1,6 +1,6 @@
 // liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies, the comparison of peers' replies,
 // the directory of an image and the answers to query_short_channel_ids, the stream index of an image and the answers to gossip_timestamp_filter,
-// the reception of channel_update batches against an image
+// the reception of channel_update and of node_announcement batches against an image
 #include "engine_internal.h"
 #include "store_audit.h"
 #include "store_repair.h"
@@ -10,6 +10,7 @@
 #include "store_query.h"
 #include "store_stream.h"
 #include "store_receive.h"
+#include "store_nodes.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <memory>
@@ -2192,6 +2193,202 @@ extern "C" int lamd_channel_update_receive_batch(lamd_ctx *ctx, const lamd_store
     const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
     if (timed) STCHK(ctx->store.t_rx.record(5, st));
     hipLaunchKernelGGL(k_rx_encode, dim3(blocks_for(adds)), block, 0, st, (u32)adds, b, (const u32 *)w.add_msg, (const u8 *)w.flags, (const u32 *)w.ts, w.hdr);
+    hipLaunchKernelGGL(k_rx_copy, dim3((unsigned)((words + 255) / 256)), block, 0, st, words,
+                       store_rx_out{w.add_off, w.add_msg, (u32)adds, w.hdr, w.msgs, w.off}, d_bytes, total);
+    STCHK(hipGetLastError());
+    if (timed) STCHK(ctx->store.t_rx.record(6, st));
+    if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  }
+  STCHK(hipStreamSynchronize(st));   // the second wait: the lists and the bytes
+  if (timed && encode) {
+    float ms = 0;
+    STCHK(hipEventElapsedTime(&ms, ctx->store.t_rx.ev[5], ctx->store.t_rx.ev[6]));
+    summary->stage_ms[4] = ms;
+  }
+  return LAMD_OK;
+}
+
+// ---- node_announcement reception (lamd_node_announcement_receive_batch; per-channel, per-message and per-row logic in store_nodes.h).  One
+// lane per channel, per message, per sorted position or per output word; each stage reads what the one before it wrote, so each is a launch
+// of its own.  The scan items, the record headers and the output words are k_rx_items', k_rx_encode's and k_rx_copy's.  cnt: RX_CNT_* words, all 0.
+// k_nr_alive: alive, one byte per node, all 0: every channel that is not dying stores a 1 for both of its nodes
+__global__ void __launch_bounds__(256) k_nr_alive(store_nr_view v, u8 *alive) {
+  const u32 c = blockIdx.x * 256 + threadIdx.x;
+  if (c < v.count + v.nbare) store_nr_alive(v, c, alive);
+}
+// k_nr_classify: statuses -1 and 1, the bisection in the ranked ids, the timestamp; the PENDING messages get consecutive signature rows with
+// one atomic per wave, as k_rx_classify's.  start / len: preset to 0 -- the rows behind the last real one are empty spans.
+__global__ void __launch_bounds__(256) k_nr_classify(store_nr_view v, store_nr_batch b, int8_t *__restrict__ status, u32 *__restrict__ node, u32 *__restrict__ ts,
+                                                     u32 *__restrict__ row_of, u64 *__restrict__ start, u64 *__restrict__ len, u32 *__restrict__ row_msg,
+                                                     u64 *__restrict__ rowbase, u32 *cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  store_nr_msg r;
+  r.status = STORE_NR_MALFORMED;
+  if (i < b.n) {
+    r = store_nr_classify(v, b, i);
+    status[i] = (int8_t)r.status;
+    node[i] = r.node;
+    ts[i] = r.ts;
+    rowbase[i] = i;
+    if (i == b.n - 1) rowbase[b.n] = b.n;
+  }
+  const bool pending = i < b.n && r.status == STORE_NR_PENDING;
+  const u32 row = wave_alloc(&cnt[RX_CNT_ROWS], pending);
+  if (i < b.n) row_of[i] = pending ? row : STORE_NONE;
+  if (pending && row < b.n) store_nr_row(b, i, row, start, len, row_msg);
+}
+__global__ void __launch_bounds__(256) k_nr_settle(u32 n, u32 pending, int8_t *__restrict__ status, u32 *__restrict__ node, const u32 *__restrict__ row_of,
+                                                   const int8_t *__restrict__ sigv, u64 *__restrict__ key, u32 *__restrict__ val) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  key[i] = store_nr_settle(status, node, row_of, sigv, pending, i);
+  val[i] = i;
+}
+__global__ void __launch_bounds__(256) k_nr_resolve(store_nr_view v, store_nr_batch b, store_rx_sorted s, const u32 *__restrict__ ts,
+                                                    const u8 *__restrict__ alive, int8_t *status, u8 *flags, store_nr_marks k, u32 *cnt) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  const bool deletes = p < s.n && store_nr_resolve(v, b, s, ts, alive, p, status, flags, k);
+  wave_count(&cnt[RX_CNT_DELS], deletes);
+}
+__global__ void __launch_bounds__(256) k_nr_plan(u32 n, const int8_t *__restrict__ status, const u64 *__restrict__ apos, const u64 *__restrict__ abyte,
+                                                 u64 add_cap, u32 *__restrict__ add_msg, u64 *__restrict__ add_off) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) store_nr_plan(status, apos, abyte, add_cap, add_msg, add_off, i);
+}
+
+// the workspace of one call, carved out of store.rx (the two receive calls of a context run one behind the other): with base == nullptr the
+// same walk gives its size
+struct nr_ws {
+  u64 *off, *start, *len, *rowbase, *key, *skey, *item, *run, *apos, *abyte, *add_off;
+  u32 *node, *ts, *row_of, *row_msg, *val, *sval, *acnt, *abytes, *del_key, *del_sorted, *add_msg, *cnt;
+  int8_t *status, *sigv;
+  u8 *flags, *alive, *hdr, *msgs, *tmp;
+  size_t bytes;
+  nr_ws(u8 *base, size_t n, size_t nodes, size_t msg_bytes, size_t tmp_bytes) {
+    size_t at = 0;
+    auto take = [&](auto **p, size_t count) {
+      using T = std::remove_reference_t<decltype(**p)>;
+      *p = base ? (T *)(base + at) : nullptr;
+      at += sizeof(T) * count;
+    };
+    take(&off, n + 1); take(&start, n); take(&len, n); take(&rowbase, n + 1); take(&key, n); take(&skey, n); take(&item, n); take(&run, n);
+    take(&apos, n + 1); take(&abyte, n + 1); take(&add_off, n + 1);
+    take(&node, n); take(&ts, n); take(&row_of, n); take(&row_msg, n); take(&val, n); take(&sval, n);
+    take(&acnt, n + 1); take(&abytes, n + 1);   // (one memset clears the two)
+    take(&del_key, n); take(&del_sorted, n); take(&add_msg, n); take(&cnt, RX_CNTS);
+    take(&status, n); take(&sigv, n); take(&flags, n); take(&alive, nodes + 1); take(&hdr, STORE_HDR * n); take(&msgs, msg_bytes + 1);
+    at = align_up(at, 256);
+    take(&tmp, tmp_bytes);
+    bytes = at + 16;
+  }
+};
+
+extern "C" int lamd_node_announcement_receive_batch(lamd_ctx *ctx, const lamd_store_directory *directory, size_t n, const uint8_t *msgs, const uint64_t *off,
+                                                    int announcements_pending, int8_t *status, uint8_t *flags, uint32_t *node, size_t add_cap,
+                                                    uint32_t *add_msg, uint64_t *add_off, uint8_t *out, void *d_out, size_t out_cap, size_t edit_cap,
+                                                    uint32_t *del_rec, lamd_node_receive_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!directory || !summary || (n && (!msgs || !off || !status || !flags || !node)) || (add_cap && (!add_msg || !add_off)) || (edit_cap && !del_rec) ||
+      n >= (size_t)STORE_NONE / 2) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  if (directory->ctx != ctx) { ctx->err = "node_announcement receive: the directory does not belong to this context"; return LAMD_ERR_ARG; }
+  if ((u64)directory->nodes >= STORE_NR_MAX_NODES) { ctx->err = "node_announcement receive: too many nodes"; return LAMD_ERR_ARG; }
+  *summary = lamd_node_receive_summary();
+  if (n == 0) return LAMD_OK;
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) { ctx->err = "node_announcement receive: decreasing message offsets"; return LAMD_ERR_ARG; }
+  const size_t msg_bytes = (size_t)(off[n] - off[0]), nodes = directory->nodes, channels = directory->count + directory->nbare;
+  std::vector<u64> rel(n + 1);   // a queued copy reads it: STCHK drains the stream
+  for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+  lamd_ctx *L = ctx;
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  size_t tmp_bytes = 0, need = 0;
+  STCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 32, st));
+  STCHK(rocprim::radix_sort_keys(nullptr, need, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 32, st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  STCHK(rocprim::inclusive_scan(nullptr, need, (const u64 *)nullptr, (u64 *)nullptr, n, rocprim::maximum<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  STCHK(rocprim::exclusive_scan(nullptr, need, (const u32 *)nullptr, (u64 *)nullptr, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.rx, nr_ws(nullptr, n, nodes, msg_bytes, tmp_bytes).bytes)) != LAMD_OK) return rc;
+  const nr_ws w(ctx->store.rx.as<u8>(), n, nodes, msg_bytes, tmp_bytes);
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_rx.create());
+  STCHK(hipMemcpyAsync(w.off, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+  if (msg_bytes) STCHK(hipMemcpyAsync(w.msgs, msgs + off[0], msg_bytes, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(w.start, 0, 16 * n, st));                  // start, len
+  STCHK(hipMemsetAsync(w.acnt, 0, 8 * (n + 1), st));              // acnt, abytes
+  STCHK(hipMemsetAsync(w.del_key, 0xFF, 4 * n, st));
+  STCHK(hipMemsetAsync(w.cnt, 0, 4 * RX_CNTS, st));
+  STCHK(hipMemsetAsync(w.flags, 0, n, st));
+  STCHK(hipMemsetAsync(w.alive, 0, nodes + 1, st));
+  const store_nr_view v{directory->img, directory->img_len, directory->rec_off, (u32)directory->n, directory->ent_rec, directory->bare_rec, directory->chan_rank,
+                        (u32)directory->count, (u32)directory->nbare, directory->node_off, directory->node_nann, (u32)nodes};
+  const store_nr_batch b{w.msgs, w.off, (u32)n, announcements_pending ? 1u : 0u};
+  const store_rx_batch eb{w.msgs, w.off, (u32)n, nullptr, 0, nullptr, 0};   // the batch as the record encoder reads it
+  const dim3 grid(blocks_for(n)), block(256);
+  if (timed) STCHK(ctx->store.t_rx.record(0, st));
+  if (channels) hipLaunchKernelGGL(k_nr_alive, dim3(blocks_for(channels)), block, 0, st, v, w.alive);
+  hipLaunchKernelGGL(k_nr_classify, grid, block, 0, st, v, b, w.status, w.node, w.ts, w.row_of, w.start, w.len, w.row_msg, w.rowbase, w.cnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(1, st));
+  // ONE signature batch over n spans, each message under its own node_id: the real rows in front, empty spans behind them
+  if ((rc = gossip_device(ctx, n, w.msgs, w.start, nullptr, w.rowbase, n, w.sigv, w.len)) != LAMD_OK) return drain_fail(ctx, L, rc);
+  if (timed) STCHK(ctx->store.t_rx.record(2, st));
+  hipLaunchKernelGGL(k_nr_settle, grid, block, 0, st, (u32)n, b.pending, w.status, w.node, (const u32 *)w.row_of, (const int8_t *)w.sigv, w.key, w.val);
+  // stable: arrival order inside a node; the ranks need 30 bits, the pads (all ones) end behind them
+  STCHK(rocprim::radix_sort_pairs(w.tmp, tmp_bytes, (const u64 *)w.key, w.skey, (const u32 *)w.val, w.sval, n, 0, 32, st));
+  hipLaunchKernelGGL(k_rx_items, grid, block, 0, st, (u32)n, (const u64 *)w.skey, (const u32 *)w.sval, (const u32 *)w.ts, w.item);
+  STCHK(rocprim::inclusive_scan(w.tmp, tmp_bytes, (const u64 *)w.item, w.run, n, rocprim::maximum<u64>(), st));
+  hipLaunchKernelGGL(k_nr_resolve, grid, block, 0, st, v, b, store_rx_sorted{w.skey, w.sval, w.run, (u32)n}, (const u32 *)w.ts, (const u8 *)w.alive, w.status,
+                     w.flags, store_nr_marks{w.acnt, w.abytes, w.del_key}, w.cnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(3, st));
+  STCHK(rocprim::radix_sort_keys(w.tmp, tmp_bytes, (const u32 *)w.del_key, w.del_sorted, n, 0, 32, st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.acnt, w.apos, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.abytes, w.abyte, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  hipLaunchKernelGGL(k_nr_plan, grid, block, 0, st, (u32)n, (const int8_t *)w.status, (const u64 *)w.apos, (const u64 *)w.abyte, (u64)n, w.add_msg, w.add_off);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(4, st));
+  u64 totals[2] = {0, 0};
+  u32 cnt[RX_CNTS] = {};
+  STCHK(hipMemcpyAsync(status, w.status, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(flags, w.flags, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(node, w.node, 4 * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[0], w.apos + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[1], w.abyte + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(cnt, w.cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: verdicts and sizes
+  if (timed) STCHK(ctx->store.t_rx.read(4, summary->stage_ms));
+  for (size_t i = 0; i < n; i++) {
+    summary->by_status[status[i] < 0 || status[i] > 6 ? 7 : status[i]]++;
+    summary->superseded += (flags[i] & STORE_RX_SUPERSEDED) != 0;
+  }
+  const u64 adds = totals[0], total = totals[1], dels = cnt[RX_CNT_DELS];
+  summary->accepted = summary->adds = adds;
+  summary->bytes = total;
+  summary->deletions = dels;
+  summary->signature_rows = cnt[RX_CNT_ROWS];
+  const bool want_out = out || d_out;
+  if (adds > add_cap) { ctx->err = "node_announcement receive: add_msg / add_off too small"; return LAMD_ERR_ARG; }
+  if (want_out && total > out_cap) { ctx->err = "node_announcement receive: output buffer too small"; return LAMD_ERR_ARG; }
+  if (dels > edit_cap) { ctx->err = "node_announcement receive: del_rec too small"; return LAMD_ERR_ARG; }
+  if (adds) {
+    STCHK(hipMemcpyAsync(add_msg, w.add_msg, 4 * adds, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(add_off, w.add_off, 8 * adds, hipMemcpyDeviceToHost, st));
+  }
+  if (dels) STCHK(hipMemcpyAsync(del_rec, w.del_sorted, 4 * dels, hipMemcpyDeviceToHost, st));
+  const bool encode = want_out && adds;
+  if (encode) {
+    if (!d_out && (rc = ensure(ctx, &ctx->store.rx_out, total + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+    u8 *d_bytes = d_out ? (u8 *)d_out : ctx->store.rx_out.as<u8>();
+    const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+    if (timed) STCHK(ctx->store.t_rx.record(5, st));
+    hipLaunchKernelGGL(k_rx_encode, dim3(blocks_for(adds)), block, 0, st, (u32)adds, eb, (const u32 *)w.add_msg, (const u8 *)w.flags, (const u32 *)w.ts, w.hdr);
     hipLaunchKernelGGL(k_rx_copy, dim3((unsigned)((words + 255) / 256)), block, 0, st, words,
                        store_rx_out{w.add_off, w.add_msg, (u32)adds, w.hdr, w.msgs, w.off}, d_bytes, total);
     STCHK(hipGetLastError());

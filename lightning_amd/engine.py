@@ -875,6 +875,49 @@ class Engine:
             res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
         return res
 
+    def node_announcement_receive(self, directory, msgs, pending=False, d_out=None, host_out=True, return_summary=False):
+        """lamd_node_announcement_receive_batch: a drained queue of raw node_announcement messages received against the image a StoreDirectory
+        was built from (by this Engine): framing, TLV tail and address descriptors, ONE signature batch under each message's own node_id, "newer
+        wins" in arrival order.  msgs: a list of messages, or (blob uint8, off uint64 [n + 1]): message i = blob[off[i]:off[i + 1]].  pending: the
+        caller's pending or too-early channel_announcement maps are not empty (an unknown node's message is held, not refused); d_out: a torch
+        uint8 CUDA tensor the added records are written to (at its data pointer, any alignment) instead of, or with host_out besides, the host.
+        -> (status int8 [msgs] (0 accepted, -1 malformed, 1 malformed addresses, 2 bad signature, 3 held, 4 unknown node, 5 stale, 6 duplicate),
+        flags uint8 [msgs] (1 SUPERSEDED, 4 DYING), node uint32 [msgs] (the rank in the directory, 0xFFFFFFFF: none), plan): plan = dict(add_msg
+        uint32 [adds], add_off uint64 [adds], records bytes or None (without host_out), del_rec uint32 ascending, set_rec / set_ts / set_crc: empty
+        uint32 arrays -- nothing is re-stamped) -- apply_update_plan() applies it to the image"""
+        if isinstance(msgs, tuple):                       # (blob uint8, off uint64 [n + 1]): a drained queue in one buffer
+            blob, off = np.ascontiguousarray(msgs[0], dtype=np.uint8), np.ascontiguousarray(msgs[1], dtype=np.uint64)
+            n = off.size - 1
+            if n < 0 or (n and int(off[n]) > blob.size):
+                raise ValueError("the offsets do not fit the blob")
+        else:
+            n = len(msgs)
+            off = np.zeros(n + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\x00", dtype=np.uint8)
+        status, flags, node = np.zeros(max(1, n), dtype=np.int8), np.zeros(max(1, n), dtype=np.uint8), np.zeros(max(1, n), dtype=np.uint32)
+        # no plan is longer than the batch: one call, no sizing pass (it would run the signature batch twice)
+        cap, nbytes = max(1, n), max(1, int(off[n] - off[0]) + 12 * n)
+        add_msg, add_off, del_rec = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+        out = np.zeros(nbytes, dtype=np.uint8) if host_out else None
+        d_ptr = None
+        if d_out is not None:
+            if d_out.numel() < nbytes:
+                raise ValueError("d_out must hold the messages and 12 bytes each")
+            self._after_torch()
+            d_ptr = d_out.data_ptr()
+        s = _ffi.LamdNodeReceiveSummary()
+        self._chk(self._lib.lamd_node_announcement_receive_batch(
+            self._ctx, directory._h, n, blob.ctypes.data, off.ctypes.data, int(bool(pending)), status.ctypes.data, flags.ctypes.data, node.ctypes.data,
+            cap, add_msg.ctypes.data, add_off.ctypes.data, None if out is None else out.ctypes.data, d_ptr, nbytes, cap, del_rec.ctypes.data, ctypes.byref(s)))
+        none = np.zeros(0, dtype=np.uint32)
+        plan = dict(add_msg=add_msg[:s.adds], add_off=add_off[:s.adds], records=None if out is None else out[:s.bytes].tobytes(), del_rec=del_rec[:s.deletions],
+                    set_rec=none, set_ts=none.copy(), set_crc=none.copy())
+        res = (status[:n], flags[:n], node[:n], plan)
+        if return_summary:
+            res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
+
     # ---- single-item veneers (reference semantics)
     def check_signed_hash(self, hash32, sig64, pubkey):
         return bool(self._chk(self._lib.lamd_check_signed_hash(self._ctx, bytes(hash32), bytes(sig64), bytes(pubkey), len(pubkey))))
