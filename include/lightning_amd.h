@@ -992,6 +992,100 @@ int lamd_node_announcement_receive_batch(lamd_ctx *ctx, const lamd_store_directo
 					 uint32_t *add_msg, uint64_t *add_off, uint8_t *out, void *d_out, size_t out_cap, size_t edit_cap,
 					 uint32_t *del_rec, lamd_node_receive_summary *summary);
 
+/* ---- receiving channel_announcement batches against a store image on the device, in the reference's two halves:
+ * gossmap_manage_channel_announcement() (gossipd/gossmap_manage.c:620-753) for a drained queue of raw messages, and
+ * gossmap_manage_handle_get_txout_reply() (:757-874) for a batch of lightningd's replies.  Between the two lies a map the caller owns: the
+ * pending and too-early queues and the txout-failure set stay with the caller, who hands them in as sorted scids.  What is not here: those
+ * maps themselves, new_block's promotion of early entries (the caller submits them again, they come back as asks), reprocess_queued_msgs, the
+ * warnings' texts, the seeker's remove_unknown_scid, and local (known_amount) announcements.
+ *
+ * 1. lamd_channel_announcement_receive_batch: message i is msgs + off[i] .. off[i + 1].  Known channels are the digest's entries plus its bare
+ * channels; the digest must come from this context (LAMD_ERR_ARG otherwise).  blockheight 0: unknown.  held_scid: the caller's pending and
+ * too-early maps together, failed_scid: its txout failures; both strictly ascending (LAMD_ERR_ARG otherwise).  There is no directory, no clock
+ * and no peer: the reference uses the source only for the warning, which stays with the caller.
+ * STATUS per message: the first that applies, in the reference's order.
+ *   -1  malformed (:644-649): shorter than 432 + flen bytes (2 + 4 * 64 + 2 + flen + 32 + 8 + 4 * 33), longer than 65535, type not 256, flen past
+ *       the end, r or s of any of the four signatures >= n, or bitcoin_key_1 / bitcoin_key_2 no valid compressed point (fromwire_pubkey).  The
+ *       node ids are NOT validated here (fromwire_node_id copies bytes): a bad id fails its signature.  Trailing bytes are legal, and signed.
+ *    1  node_id_1 is not memcmp-less than node_id_2 (:659-663)
+ *    2  foreign chain (:669-670)
+ *    3  the scid is in failed_scid (:677-679)
+ *    4  known: a digest entry, a bare channel, or in held_scid (:682-685)
+ *    5 .. 8  bad node_signature_1, node_signature_2, bitcoin_signature_1, bitcoin_signature_2: the first that fails (sigcheck.c:78-113)
+ *    9  bad gossip order: blockheight != 0 and blocknum(scid) > blockheight + 12 (:722-728)
+ *   10  already pending from this batch: an EARLIER message of the batch with the same scid got status 0 or 11 (the map_get of :683-684 seeing
+ *       what that message left).  It sits in front of the signature check: a later copy with damaged signatures gets 10, not 5 .. 8; a copy
+ *       in front of the first good one gets its own 5 .. 8.
+ *   11  early: blocknum + 5 > blockheight, blockheight 0 included (is_scid_depth_announceable).  The caller keeps it in its too-early map.
+ *    0  pending: the caller keeps it and asks lightningd.
+ * scid[i]: the message's short_channel_id; 0 for status -1.
+ * spk34[34 i ..]: for the statuses 0 and 11 scriptpubkey_p2wsh(bitcoin_redeem_2of2()) -- 00 20 SHA256(52 21 <lesser key> 21 <greater key> 52 ae),
+ *   the keys ordered by memcmp of their 33 bytes (bitcoin/script.c:149-165) --, 34 zero bytes otherwise.
+ * THE ASK LIST  ask_msg[j], ask_scid[j], j < asks: the messages of status 0 in arrival order -- the get_txout requests.
+ * SIZES  ask_cap must hold the asks.  Too small: LAMD_ERR_ARG with summary, status, scid and spk34 filled in and nothing written to the list.
+ *   ask_cap 0: the verdicts and the size alone.
+ * Device work, on the context's stream: k_ca_classify (one lane per message, byte loads at any alignment: framing, the eight scalars, statuses
+ * 1 .. 4 by comparisons and four bisections; the rows compacted into TWO lists with one atomic per wave each), ONE signature batch over the spans
+ * of the messages that passed the filters, four rows each (a bitcoin key that does not parse makes the message malformed), the key validity
+ * kernel over the two bitcoin keys of the messages a filter dropped (the reference calls them malformed BEFORE its filters) -- a batch of known
+ * channels costs no signature --, k_ca_settle, a stable rocPRIM radix sort by the 64-bit scid, an inclusive minimum scan by key over the
+ * arrival indexes of the good copies, k_ca_resolve per sorted position (statuses 5 .. 11 and 0; no walk of a scid's messages), an exclusive
+ * scan in arrival order, k_ca_script (two SHA-256 compressions per lane, the ask list).  The host waits for the two lists' lengths (eight
+ * bytes), once for the verdicts and sizes and once for the ask list.  Limits: n below 2^30, off non-decreasing. */
+typedef struct {
+	uint64_t by_status[13];     /* messages: [0] .. [11] statuses 0 .. 11, [12] malformed */
+	uint64_t asks;              /* what ask_cap must hold */
+	uint64_t signature_rows;    /* the rows of the signature batch: 4 per message that passed the filters */
+	uint64_t keyparse_rows;     /* the keys parsed alone: 2 per message a filter dropped */
+	double stage_ms[4];         /* with lamd_set_timing: classify, signatures and keys, resolve, scripts */
+} lamd_announce_receive_summary;
+int lamd_channel_announcement_receive_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, uint32_t blockheight,
+					    size_t n, const uint8_t *msgs, const uint64_t *off, size_t n_held, const uint64_t *held_scid,
+					    size_t n_failed, const uint64_t *failed_scid, int8_t *status, uint64_t *scid, uint8_t *spk34,
+					    size_t ask_cap, uint32_t *ask_msg, uint64_t *ask_scid, lamd_announce_receive_summary *summary);
+
+/* 2. lamd_channel_announcement_confirm_batch: digest and directory of the image as it is NOW (one image, this context).  The caller's pending
+ * announcements: np raw messages, pending message p = pend_msgs + pend_off[p] .. pend_off[p + 1], well framed and STRICTLY ASCENDING by scid, as the
+ * reference's uintmap iterates (anything else: LAMD_ERR_ARG), with their scripts from call 1 in pend_spk34.  nr replies in arrival order: r_scid,
+ * r_sat, script r = r_scripts + r_script_off[r] .. r_script_off[r + 1].
+ * STATUS per reply, in the reference's order.
+ *    1  no pending announcement of that scid (:771-782) -- every reply behind the FIRST one of the same scid in the batch included: map_del
+ *       consumed the entry whatever became of it
+ *    2  empty script: no unspent output (:791-810)
+ *    3  the script is not byte-equal to the pending one; a length other than 34 fails here (:812-819)
+ *    4  redundant: the scid is a digest entry or a bare channel (:822-847).  Dropped, and NOT a txout failure.
+ *    0  accepted
+ * pend[r]: the index of the pending message the reply consumed, UINT32_MAX for status 1.
+ * fail_scid[k], k < failures: the scids of the statuses 2 and 3 in reply order; the caller adds them to its failure set.
+ * THE PLAN
+ *   add_reply[j], add_off[j], j < adds: per accepted reply, in reply order, TWO records back to back, the first at add_off[j]: the announcement --
+ *     be16 flags 0x2000, be16 len, be32 crc32c seeded with timestamp 0, be32 timestamp 0, the message -- and gossip_store_channel_amount --
+ *     the same header over 10 bytes: be16 4101, be64 sat (:850-852, gossip_store.c:49-78).
+ *   clr_rec[k], k < clears: node_announcements_not_dying() (:603-618) for both node ids of every accepted announcement: the node's announcement
+ *     record in force (the directory's nann_rec) where its header carries 0x0800; ascending, each record once.  Clear 0x08 of byte 0 of those
+ *     headers; the flag lies outside the CRC.
+ *   There are no deletions and no re-stamps.
+ * SIZES  add_cap must hold the adds, fail_cap the failures, clr_cap the clears, out_cap the bytes (when out or d_out is given).  One too small:
+ *   LAMD_ERR_ARG with summary, status and pend filled in and nothing written to the lists, out or d_out.  All caps 0: the verdicts and sizes alone.
+ *   The bytes go to out (host), d_out (device, any alignment), or neither.
+ * Device work: k_ca_match (a bisection per reply, one 32-bit atomicMin of the reply index per pending slot), k_ca_confirm (the status; per
+ * accepted node id a 33-byte bisection and the header of its record), a sort of the dying records and k_ca_clr_heads / k_ca_clr_write (unique),
+ * exclusive scans in reply order, k_ca_plan, and behind the first wait the update call's k_rx_encode and k_rx_copy.  The host waits once for the
+ * verdicts and sizes and once for the lists and bytes.  Limits: np and nr below 2^30. */
+typedef struct {
+	uint64_t by_status[5];      /* replies: statuses 0 .. 4 */
+	uint64_t adds, bytes;       /* what add_cap and out_cap must hold */
+	uint64_t failures;          /* what fail_cap must hold */
+	uint64_t clears;            /* what clr_cap must hold */
+	double stage_ms[3];         /* with lamd_set_timing: classify, plan, encode */
+} lamd_announce_confirm_summary;
+int lamd_channel_announcement_confirm_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const lamd_store_directory *directory, size_t np,
+					    const uint8_t *pend_msgs, const uint64_t *pend_off, const uint8_t *pend_spk34, size_t nr,
+					    const uint64_t *r_scid, const uint64_t *r_sat, const uint8_t *r_scripts, const uint64_t *r_script_off,
+					    int8_t *status, uint32_t *pend, size_t add_cap, uint32_t *add_reply, uint64_t *add_off, uint8_t *out,
+					    void *d_out, size_t out_cap, size_t fail_cap, uint64_t *fail_scid, size_t clr_cap, uint32_t *clr_rec,
+					    lamd_announce_confirm_summary *summary);
+
 /* ---- streaming front end for callers that produce triples one at a time (channeld's
  * commitment_signed loop, channeld/channeld.c:2171,2215-2232; gossip ingest).  Triples are
  * appended to a pinned staging set; flush launches everything queued so far as one batch (asynchronous) and opens the

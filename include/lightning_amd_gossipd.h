@@ -27,7 +27,10 @@
  * query_short_channel_ids responder is lamd_short_channel_ids_reply_batch and a peer's gossip_timestamp_filter is answered by
  * lamd_timestamp_filter_reply_batch, both from the same image; the per-peer state of a stream -- gossip_rcvd_filter, the 60-second
  * timer, dev_suppress_gossip -- stays with the caller; the channel_update half of step 1 - 3 against such an image, look-ups and replay on
- * the device, is lamd_channel_update_receive_batch) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
+ * the device, is lamd_channel_update_receive_batch, the node_announcement half lamd_node_announcement_receive_batch, and the
+ * channel_announcement half with its txout replies lamd_channel_announcement_receive_batch / lamd_channel_announcement_confirm_batch: with them
+ * every gossip message can be received against an image; what stays with the caller there are the pending, too-early and txout-failure maps
+ * themselves, new_block's promotion of early entries, reprocess_queued_msgs, the warnings' texts and the seeker) -- events tell the host daemon what the reference would have done (send a warning, ask lightningd for a txout,
  * append to / delete from / re-flag the store) and it does the I/O.
  *
  * Everything observable is reported through the event callback, in the order the reference would produce it; texts

@@ -110,6 +110,18 @@ class LamdNodeReceiveSummary(ctypes.Structure):
                 ("bytes", ctypes.c_uint64), ("deletions", ctypes.c_uint64), ("signature_rows", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 5)]
 
 
+class LamdAnnounceReceiveSummary(ctypes.Structure):
+    """lamd_announce_receive_summary (include/lightning_amd.h): what lamd_channel_announcement_receive_batch reports about a batch of channel_announcements"""
+    _fields_ = [("by_status", ctypes.c_uint64 * 13), ("asks", ctypes.c_uint64), ("signature_rows", ctypes.c_uint64), ("keyparse_rows", ctypes.c_uint64),
+                ("stage_ms", ctypes.c_double * 4)]
+
+
+class LamdAnnounceConfirmSummary(ctypes.Structure):
+    """lamd_announce_confirm_summary (include/lightning_amd.h): what lamd_channel_announcement_confirm_batch reports about a batch of txout replies"""
+    _fields_ = [("by_status", ctypes.c_uint64 * 5), ("adds", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("failures", ctypes.c_uint64),
+                ("clears", ctypes.c_uint64), ("stage_ms", ctypes.c_double * 3)]
+
+
 class LamdGtableAuditResult(ctypes.Structure):
     """lamd_gtable_audit_result (include/lightning_amd_debug.h): what lamd_debug_gtable_audit found in a range of the static G table"""
     _fields_ = [("bad", ctypes.c_uint64), ("first_bad", ctypes.c_uint64), ("first_reason", ctypes.c_uint32), ("n_list", ctypes.c_uint32),
@@ -195,6 +207,11 @@ SYMBOLS = {
                                                          c_u8p, c_u8p, c_u8p, ctypes.POINTER(LamdUpdateReceiveSummary)]),
     "lamd_node_announcement_receive_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_sz, c_u8p, c_u8p, ctypes.c_int, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
                                                             c_u8p, ctypes.c_void_p, c_sz, c_sz, c_u8p, ctypes.POINTER(LamdNodeReceiveSummary)]),
+    "lamd_channel_announcement_receive_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_sz, c_u8p, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_u8p,
+                                                               c_u8p, c_u8p, c_sz, c_u8p, c_u8p, ctypes.POINTER(LamdAnnounceReceiveSummary)]),
+    "lamd_channel_announcement_confirm_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_sz, c_u8p, c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, c_u8p,
+                                                               c_u8p, c_u8p, c_sz, c_u8p, c_u8p, c_u8p, ctypes.c_void_p, c_sz, c_sz, c_u8p, c_sz, c_u8p,
+                                                               ctypes.POINTER(LamdAnnounceConfirmSummary)]),
     "lamd_selftest": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, ctypes.c_char_p, c_sz]),
     "lamd_chain_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, c_sz]),
     "lamd_inv_debug": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, c_sz]),

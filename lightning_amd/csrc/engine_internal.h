@@ -197,10 +197,10 @@ struct lamd_ctx {
   // block sums, node table, and the output image; digest build: its tables and the sort's workspace; range replies: plan arrays, the messages;
   // range comparison: the peers' messages, classes, lists, the sorts' workspace, and the queries it writes; directory build: candidates, keys,
   // permutations, the sorts' workspace; short_channel_ids replies: the queries, per-occurrence and per-node arrays, offsets, and the messages.
-  // channel_update and node_announcement reception (rx, rx_out, t_rx: one call at a time): the batch, its per-message, per-row and per-slot
-  // arrays, the plan, and the added records.
+  // channel_update, node_announcement and channel_announcement reception, the txout replies included (rx, rx_out, t_rx: one call at a time): the
+  // batch, its per-message, per-row and per-slot arrays, the plan, and the added records.
   // t_audit / t_rep: the stage boundaries of an audit and of a repair's own stages; t_dig: those of a digest or directory build, a range reply, a
-  // comparison, a short_channel_ids reply, a stream index build or a timestamp filter reply; t_rx: those of a channel_update or node_announcement reception
+  // comparison, a short_channel_ids reply, a stream index build or a timestamp filter reply; t_rx: those of a reception call (channel_update, node_announcement, channel_announcement, txout replies)
   struct store_ws {
     devbuf img, host, ids, tab, out, rep, pack, dig, rng, rng_out, cmp, cmp_out, dir, sq, sq_out, ts, ts_msg, ts_out, rx, rx_out;
     stage_timer<6> t_audit;

@@ -1,6 +1,6 @@
 // liblightning_amd.so, the gossip_store calls: audit, repair, latest-wins repair, digest, channel-range replies, the comparison of peers' replies,
 // the directory of an image and the answers to query_short_channel_ids, the stream index of an image and the answers to gossip_timestamp_filter,
-// the reception of channel_update and of node_announcement batches against an image
+// the reception of channel_update, node_announcement and channel_announcement batches against an image
 #include "engine_internal.h"
 #include "store_audit.h"
 #include "store_repair.h"
@@ -11,8 +11,10 @@
 #include "store_stream.h"
 #include "store_receive.h"
 #include "store_nodes.h"
+#include "store_announce.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_scan_by_key.hpp>
 #include <memory>
 
 // ---- gossip_store audit (lamd_gossip_store_audit; per-record logic in store_audit.h).  One lane per record throughout.
@@ -2400,6 +2402,375 @@ extern "C" int lamd_node_announcement_receive_batch(lamd_ctx *ctx, const lamd_st
     float ms = 0;
     STCHK(hipEventElapsedTime(&ms, ctx->store.t_rx.ev[5], ctx->store.t_rx.ev[6]));
     summary->stage_ms[4] = ms;
+  }
+  return LAMD_OK;
+}
+
+// ---- channel_announcement reception, both halves (lamd_channel_announcement_receive_batch / _confirm_batch; per-message, per-position and
+// per-reply logic in store_announce.h).  One lane per message, per sorted position, per reply or per output word; each stage reads what the one
+// before it wrote, so each is a launch of its own.  The record headers and the output words are k_rx_encode's and k_rx_copy's.
+enum { CA_CNT_SIGS = 0, CA_CNT_KEYS = 1, CA_CNTS = 4 };
+// k_ca_classify: the framing half of -1 and statuses 1 .. 4; the rows of the TWO lists with one atomic per wave each: a message that passed the
+// filters gets a span of the signature batch, a message a filter dropped gets its two bitcoin keys parsed.  rowbase: four rows per span.
+__global__ void __launch_bounds__(256) k_ca_classify(store_ca_view v, store_ca_batch b, int8_t *__restrict__ status, u64 *__restrict__ scid, u32 *__restrict__ keyoff,
+                                                     u8 *__restrict__ list, u32 *__restrict__ row_of, u64 *__restrict__ start, u64 *__restrict__ len,
+                                                     u64 *__restrict__ rowbase, u8 *__restrict__ keys33, u32 *cnt) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  store_ca_msg r;
+  r.status = STORE_CA_MALFORMED;
+  r.list = STORE_CA_LIST_NONE;
+  r.keyoff = 0;
+  if (i < b.n) {
+    r = store_ca_classify(v, b, i);
+    status[i] = (int8_t)r.status;
+    scid[i] = r.scid;
+    keyoff[i] = r.keyoff;
+    list[i] = (u8)r.list;
+    rowbase[i] = 4 * (u64)i;
+    if (i == b.n - 1) rowbase[b.n] = 4 * (u64)b.n;
+  }
+  const bool sig = i < b.n && r.list == STORE_CA_LIST_SIGNATURES, key = i < b.n && r.list == STORE_CA_LIST_KEYS;
+  const u32 srow = wave_alloc(&cnt[CA_CNT_SIGS], sig), krow = wave_alloc(&cnt[CA_CNT_KEYS], key);
+  if (i < b.n) row_of[i] = sig ? srow : key ? krow : STORE_NONE;
+  if (sig && srow < b.n) store_ca_sig_row(b, i, srow, start, len);
+  if (key && krow < b.n) store_ca_key_row(b, i, r.keyoff, krow, keys33);
+}
+__global__ void __launch_bounds__(256) k_ca_settle(u32 n, u32 blockheight, int8_t *__restrict__ status, u64 *__restrict__ scid, const u8 *__restrict__ list,
+                                                   const u32 *__restrict__ row_of, const int8_t *__restrict__ sigv, const u8 *__restrict__ keyok,
+                                                   u64 *__restrict__ key, u32 *__restrict__ item, u32 *__restrict__ val) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const u64 k = scid[i];   // (the sort key is the scid the message carries, malformed or not: only candidates are resolved)
+  item[i] = store_ca_settle(status, scid, list, row_of, sigv, keyok, blockheight, i);
+  key[i] = k;
+  val[i] = i;
+}
+__global__ void __launch_bounds__(256) k_ca_items(u32 n, const u32 *__restrict__ sval, const u32 *__restrict__ item, u32 *__restrict__ sitem) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  if (p < n) sitem[p] = item[sval[p]];
+}
+__global__ void __launch_bounds__(256) k_ca_resolve(u32 n, u32 blockheight, const u32 *__restrict__ sval, const u32 *__restrict__ first,
+                                                    const u64 *__restrict__ scid, int8_t *status, u32 *acnt) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  if (p < n) store_ca_resolve(sval, first, scid, blockheight, p, status, acnt);
+}
+// k_ca_script: scriptpubkey_p2wsh(bitcoin_redeem_2of2()) of the pending and early messages, two compressions per lane; the ask list
+__global__ void __launch_bounds__(256) k_ca_script(store_ca_batch b, const int8_t *__restrict__ status, const u64 *__restrict__ scid,
+                                                   const u32 *__restrict__ keyoff, const u64 *__restrict__ apos, u64 ask_cap, u8 *__restrict__ spk34,
+                                                   u32 *__restrict__ ask_msg, u64 *__restrict__ ask_scid) {
+  const u32 i = blockIdx.x * 256 + threadIdx.x;
+  if (i < b.n) store_ca_finish(b, status, scid, keyoff, apos, ask_cap, spk34, ask_msg, ask_scid, i);
+}
+
+// the workspace of one call, carved out of store.rx (the receive calls of a context run one behind the other)
+struct ca_ws {
+  u64 *off, *start, *len, *rowbase, *scid, *key, *skey, *apos, *ask_scid, *held, *failed;
+  u32 *keyoff, *row_of, *val, *sval, *item, *sitem, *first, *acnt, *ask_msg, *cnt, *qwords;
+  int8_t *status, *sigv;
+  u8 *list, *keys33, *keyok, *spk, *msgs, *tmp;
+  size_t bytes;
+  ca_ws(u8 *base, size_t n, size_t n_held, size_t n_failed, size_t msg_bytes, size_t tmp_bytes) {
+    size_t at = 0;
+    auto take = [&](auto **p, size_t count) {
+      using T = std::remove_reference_t<decltype(**p)>;
+      *p = base ? (T *)(base + at) : nullptr;
+      at += sizeof(T) * count;
+    };
+    take(&off, n + 1); take(&start, n); take(&len, n); take(&rowbase, n + 1); take(&scid, n); take(&key, n); take(&skey, n); take(&apos, n + 1);
+    take(&ask_scid, n); take(&held, n_held); take(&failed, n_failed);
+    take(&qwords, 32 * n);   // 64 bytes per key, two keys per message
+    take(&keyoff, n); take(&row_of, n); take(&val, n); take(&sval, n); take(&item, n); take(&sitem, n); take(&first, n); take(&acnt, n + 1);
+    take(&ask_msg, n); take(&cnt, CA_CNTS);
+    take(&status, n); take(&sigv, n); take(&list, n); take(&keys33, 66 * n); take(&keyok, 2 * n); take(&spk, STORE_CA_SPK * n); take(&msgs, msg_bytes + 1);
+    at = align_up(at, 256);
+    take(&tmp, tmp_bytes);
+    bytes = at + 16;
+  }
+};
+
+extern "C" int lamd_channel_announcement_receive_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const uint8_t *chain_hash32, uint32_t blockheight,
+                                                       size_t n, const uint8_t *msgs, const uint64_t *off, size_t n_held, const uint64_t *held_scid,
+                                                       size_t n_failed, const uint64_t *failed_scid, int8_t *status, uint64_t *scid, uint8_t *spk34,
+                                                       size_t ask_cap, uint32_t *ask_msg, uint64_t *ask_scid, lamd_announce_receive_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!digest || !chain_hash32 || !summary || (n && (!msgs || !off || !status || !scid || !spk34)) || (ask_cap && (!ask_msg || !ask_scid)) ||
+      (n_held && !held_scid) || (n_failed && !failed_scid) || n >= (size_t)STORE_NONE / 4 || n_held >= (size_t)STORE_NONE || n_failed >= (size_t)STORE_NONE) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  if (digest->ctx != ctx) { ctx->err = "channel_announcement receive: the digest does not belong to this context"; return LAMD_ERR_ARG; }
+  *summary = lamd_announce_receive_summary();
+  if (n == 0) return LAMD_OK;
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) { ctx->err = "channel_announcement receive: decreasing message offsets"; return LAMD_ERR_ARG; }
+  for (size_t k = 1; k < n_held; k++)
+    if (held_scid[k] <= held_scid[k - 1]) { ctx->err = "channel_announcement receive: held_scid is not ascending"; return LAMD_ERR_ARG; }
+  for (size_t k = 1; k < n_failed; k++)
+    if (failed_scid[k] <= failed_scid[k - 1]) { ctx->err = "channel_announcement receive: failed_scid is not ascending"; return LAMD_ERR_ARG; }
+  const size_t msg_bytes = (size_t)(off[n] - off[0]);
+  std::vector<u64> rel(n + 1);   // a queued copy reads it: STCHK drains the stream
+  for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+  lamd_ctx *L = ctx;
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  size_t tmp_bytes = 0, need = 0;
+  STCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 64, st));
+  STCHK(rocprim::inclusive_scan_by_key(nullptr, need, (const u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, rocprim::minimum<u32>(),
+                                       rocprim::equal_to<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  STCHK(rocprim::exclusive_scan(nullptr, need, (const u32 *)nullptr, (u64 *)nullptr, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.rx, ca_ws(nullptr, n, n_held, n_failed, msg_bytes, tmp_bytes).bytes)) != LAMD_OK) return rc;
+  const ca_ws w(ctx->store.rx.as<u8>(), n, n_held, n_failed, msg_bytes, tmp_bytes);
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_rx.create());
+  STCHK(hipMemcpyAsync(w.off, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+  if (msg_bytes) STCHK(hipMemcpyAsync(w.msgs, msgs + off[0], msg_bytes, hipMemcpyHostToDevice, st));
+  if (n_held) STCHK(hipMemcpyAsync(w.held, held_scid, 8 * n_held, hipMemcpyHostToDevice, st));
+  if (n_failed) STCHK(hipMemcpyAsync(w.failed, failed_scid, 8 * n_failed, hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(w.acnt, 0, 4 * (n + 1), st));
+  STCHK(hipMemsetAsync(w.cnt, 0, 4 * CA_CNTS, st));
+  const store_ca_view v{digest->scid, (u32)digest->count, digest->bare, (u32)digest->nbare};
+  store_ca_batch b{w.msgs, w.off, (u32)n, w.held, (u32)n_held, w.failed, (u32)n_failed, blockheight, {}};
+  memcpy(b.chain, chain_hash32, 32);
+  const dim3 grid(blocks_for(n)), block(256);
+  if (timed) STCHK(ctx->store.t_rx.record(0, st));
+  hipLaunchKernelGGL(k_ca_classify, grid, block, 0, st, v, b, w.status, w.scid, w.keyoff, w.list, w.row_of, w.start, w.len, w.rowbase, w.keys33, w.cnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(1, st));
+  // the lengths of the two lists: eight bytes the host waits for, so that a batch of known channels costs no signature row at all (four
+  // all-zero rows per message would be what the ecmult still walks)
+  u32 cnt[CA_CNTS] = {};
+  STCHK(hipMemcpyAsync(cnt, w.cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));
+  const size_t sigs = cnt[CA_CNT_SIGS], keys = cnt[CA_CNT_KEYS];
+  if (sigs > n || keys > n || sigs + keys > n) { ctx->err = "channel_announcement receive: the lists are longer than the batch"; return LAMD_ERR_HIP; }
+  // ONE signature batch over the spans of the signature list, four rows each, every signer taken from its message
+  if (sigs && (rc = gossip_device(ctx, sigs, w.msgs, w.start, nullptr, w.rowbase, 4 * sigs, w.sigv, w.len)) != LAMD_OK) return drain_fail(ctx, L, rc);
+  // the key-parse list: the validity bytes of its bitcoin keys (the kernel behind lamd_pubkey_parse_batch)
+  if (keys && (rc = launch_key_validity(ctx, st, 2 * keys, w.keys33, w.qwords, w.keyok)) != LAMD_OK) return drain_fail(ctx, L, rc);
+  if (timed) STCHK(ctx->store.t_rx.record(2, st));
+  hipLaunchKernelGGL(k_ca_settle, grid, block, 0, st, (u32)n, blockheight, w.status, w.scid, (const u8 *)w.list, (const u32 *)w.row_of, (const int8_t *)w.sigv,
+                     (const u8 *)w.keyok, w.key, w.item, w.val);
+  // stable: arrival order inside a scid, all 64 bits of it
+  STCHK(rocprim::radix_sort_pairs(w.tmp, tmp_bytes, (const u64 *)w.key, w.skey, (const u32 *)w.val, w.sval, n, 0, 64, st));
+  hipLaunchKernelGGL(k_ca_items, grid, block, 0, st, (u32)n, (const u32 *)w.sval, (const u32 *)w.item, w.sitem);
+  STCHK(rocprim::inclusive_scan_by_key(w.tmp, tmp_bytes, (const u64 *)w.skey, (const u32 *)w.sitem, w.first, n, rocprim::minimum<u32>(),
+                                       rocprim::equal_to<u64>(), st));
+  hipLaunchKernelGGL(k_ca_resolve, grid, block, 0, st, (u32)n, blockheight, (const u32 *)w.sval, (const u32 *)w.first, (const u64 *)w.scid, w.status, w.acnt);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(3, st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.acnt, w.apos, (u64)0, n + 1, rocprim::plus<u64>(), st));
+  hipLaunchKernelGGL(k_ca_script, grid, block, 0, st, b, (const int8_t *)w.status, (const u64 *)w.scid, (const u32 *)w.keyoff, (const u64 *)w.apos, (u64)n, w.spk,
+                     w.ask_msg, w.ask_scid);
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(4, st));
+  u64 asks = 0;
+  STCHK(hipMemcpyAsync(status, w.status, n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(scid, w.scid, 8 * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(spk34, w.spk, STORE_CA_SPK * n, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&asks, w.apos + n, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: verdicts and sizes
+  if (timed) STCHK(ctx->store.t_rx.read(4, summary->stage_ms));
+  for (size_t i = 0; i < n; i++) summary->by_status[status[i] < 0 || status[i] > 11 ? 12 : status[i]]++;
+  summary->asks = asks;
+  summary->signature_rows = 4 * sigs;
+  summary->keyparse_rows = 2 * keys;
+  if (asks > ask_cap) { ctx->err = "channel_announcement receive: ask_msg / ask_scid too small"; return LAMD_ERR_ARG; }
+  if (asks) {
+    STCHK(hipMemcpyAsync(ask_msg, w.ask_msg, 4 * asks, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(ask_scid, w.ask_scid, 8 * asks, hipMemcpyDeviceToHost, st));
+    STCHK(hipStreamSynchronize(st));   // the second wait: the ask list
+  }
+  return LAMD_OK;
+}
+
+// ---- the replies.  k_ca_match: the pending announcement of every reply, the first reply of every pending slot (one 32-bit atomicMin)
+__global__ void __launch_bounds__(256) k_ca_match(store_cf_batch b, u32 *__restrict__ pend, u32 *first) {
+  const u32 r = blockIdx.x * 256 + threadIdx.x;
+  if (r < b.nr) store_cf_match(b, r, pend, first);
+}
+__global__ void __launch_bounds__(256) k_ca_confirm(store_cf_view v, store_cf_batch b, int8_t *__restrict__ status, u32 *__restrict__ pend,
+                                                    const u32 *__restrict__ first, store_cf_marks k) {
+  const u32 r = blockIdx.x * 256 + threadIdx.x;
+  if (r < b.nr) status[r] = (int8_t)store_cf_classify(v, b, r, pend, first, k);
+}
+__global__ void __launch_bounds__(256) k_ca_clr_heads(u32 m, const u32 *__restrict__ sorted, u32 *__restrict__ head) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  if (p < m) head[p] = store_cf_clr_head(sorted, p);
+}
+__global__ void __launch_bounds__(256) k_ca_clr_write(u32 m, const u32 *__restrict__ sorted, const u32 *__restrict__ head, const u64 *__restrict__ pos,
+                                                      u32 *__restrict__ clr) {
+  const u32 p = blockIdx.x * 256 + threadIdx.x;
+  if (p < m && head[p]) clr[pos[p]] = sorted[p];
+}
+__global__ void __launch_bounds__(256) k_ca_plan(store_cf_batch b, const int8_t *__restrict__ status, const u32 *__restrict__ pend, const u64 *__restrict__ apos,
+                                                 const u64 *__restrict__ abyte, const u64 *__restrict__ fpos, store_cf_plan_out o) {
+  const u32 r = blockIdx.x * 256 + threadIdx.x;
+  if (r < b.nr) store_cf_plan(b, status, pend, apos, abyte, fpos, o, r);
+}
+
+// the workspace of one confirm call, carved out of store.rx.  msgs: the pending messages, then ten bytes per reply for the amount messages
+struct cf_ws {
+  u64 *off2, *pscid, *r_scid, *r_sat, *soff, *apos, *abyte, *fpos, *cpos, *add_off, *fail_scid, *rec_off;
+  u32 *pend, *first, *acnt, *abytes, *fcnt, *clr_key, *clr_sorted, *clr_head, *clr, *add_reply, *rec_msg, *zero;
+  int8_t *status;
+  u8 *pspk, *scripts, *hdr, *flags0, *msgs, *tmp;
+  size_t bytes;
+  cf_ws(u8 *base, size_t np, size_t nr, size_t msg_bytes, size_t script_bytes, size_t tmp_bytes) {
+    size_t at = 0;
+    auto take = [&](auto **p, size_t count) {
+      using T = std::remove_reference_t<decltype(**p)>;
+      *p = base ? (T *)(base + at) : nullptr;
+      at += sizeof(T) * count;
+    };
+    take(&off2, np + nr + 1); take(&pscid, np); take(&r_scid, nr); take(&r_sat, nr); take(&soff, nr + 1); take(&apos, nr + 1); take(&abyte, nr + 1);
+    take(&fpos, nr + 1); take(&cpos, 2 * nr + 1); take(&add_off, nr); take(&fail_scid, nr); take(&rec_off, 2 * nr + 1);
+    take(&pend, nr); take(&first, np);
+    take(&acnt, nr + 1); take(&abytes, nr + 1); take(&fcnt, nr + 1);   // (one memset clears the three)
+    take(&clr_key, 2 * nr); take(&clr_sorted, 2 * nr); take(&clr_head, 2 * nr + 1); take(&clr, 2 * nr); take(&add_reply, nr); take(&rec_msg, 2 * nr);
+    take(&zero, np + nr);    // the timestamps of the records: all 0
+    take(&status, nr); take(&pspk, STORE_CA_SPK * np); take(&scripts, script_bytes + 1); take(&hdr, STORE_HDR * 2 * nr); take(&flags0, np + nr);
+    take(&msgs, msg_bytes + STORE_CA_AMOUNT * nr + 1);
+    at = align_up(at, 256);
+    take(&tmp, tmp_bytes);
+    bytes = at + 16;
+  }
+};
+
+extern "C" int lamd_channel_announcement_confirm_batch(lamd_ctx *ctx, const lamd_store_digest *digest, const lamd_store_directory *directory, size_t np,
+                                                       const uint8_t *pend_msgs, const uint64_t *pend_off, const uint8_t *pend_spk34, size_t nr,
+                                                       const uint64_t *r_scid, const uint64_t *r_sat, const uint8_t *r_scripts, const uint64_t *r_script_off,
+                                                       int8_t *status, uint32_t *pend, size_t add_cap, uint32_t *add_reply, uint64_t *add_off, uint8_t *out,
+                                                       void *d_out, size_t out_cap, size_t fail_cap, uint64_t *fail_scid, size_t clr_cap, uint32_t *clr_rec,
+                                                       lamd_announce_confirm_summary *summary) {
+  if (!ctx) return LAMD_ERR_ARG;
+  if (!digest || !directory || !summary || (np && (!pend_msgs || !pend_off || !pend_spk34)) || (nr && (!r_scid || !r_sat || !r_script_off || !status || !pend)) ||
+      (add_cap && (!add_reply || !add_off)) || (fail_cap && !fail_scid) || (clr_cap && !clr_rec) || np >= (size_t)STORE_NONE / 4 || nr >= (size_t)STORE_NONE / 4) {
+    ctx->err = "bad argument";
+    return LAMD_ERR_ARG;
+  }
+  // the digest and the directory of ONE image, built by this context
+  if (digest->ctx != ctx || directory->ctx != ctx || directory->n != digest->cap || directory->count != digest->count || directory->nbare != digest->nbare) {
+    ctx->err = "channel_announcement confirm: the digest and the directory do not belong to this context and to one image";
+    return LAMD_ERR_ARG;
+  }
+  *summary = lamd_announce_confirm_summary();
+  // the pending announcements as the caller's map iterates them: well framed, strictly ascending by scid
+  std::vector<u64> pscid(np), rel(np + nr + 1), srel(nr + 1);
+  for (size_t p = 0; p < np; p++) {
+    if (pend_off[p + 1] < pend_off[p]) { ctx->err = "channel_announcement confirm: decreasing message offsets"; return LAMD_ERR_ARG; }
+    const u8 *m = pend_msgs + pend_off[p];
+    const size_t len = (size_t)(pend_off[p + 1] - pend_off[p]);
+    if (len < STORE_CA_MIN || len > STORE_CA_MAX || store_be16(m) != STORE_T_CANN) { ctx->err = "channel_announcement confirm: a pending message is no channel_announcement"; return LAMD_ERR_ARG; }
+    const gossip_frame f = gossip_parse_frame(m, len);
+    if (f.bad) { ctx->err = "channel_announcement confirm: a pending message is no channel_announcement"; return LAMD_ERR_ARG; }
+    pscid[p] = store_be64(m + f.keyoff - 8);
+    if (p && pscid[p] <= pscid[p - 1]) { ctx->err = "channel_announcement confirm: the pending announcements are not strictly ascending by scid"; return LAMD_ERR_ARG; }
+  }
+  if (nr == 0) return LAMD_OK;
+  for (size_t r = 0; r < nr; r++)
+    if (r_script_off[r + 1] < r_script_off[r]) { ctx->err = "channel_announcement confirm: decreasing script offsets"; return LAMD_ERR_ARG; }
+  const size_t msg_bytes = np ? (size_t)(pend_off[np] - pend_off[0]) : 0, script_bytes = (size_t)(r_script_off[nr] - r_script_off[0]);
+  if (script_bytes && !r_scripts) { ctx->err = "bad argument"; return LAMD_ERR_ARG; }
+  for (size_t p = 0; p <= np; p++) rel[p] = np ? pend_off[p] - pend_off[0] : 0;
+  for (size_t j = 1; j <= nr; j++) rel[np + j] = 0;   // (k_ca_plan writes the offsets of the amount messages)
+  for (size_t r = 0; r <= nr; r++) srel[r] = r_script_off[r] - r_script_off[0];
+  lamd_ctx *L = ctx;
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  size_t tmp_bytes = 0, need = 0;
+  STCHK(rocprim::radix_sort_keys(nullptr, tmp_bytes, (const u32 *)nullptr, (u32 *)nullptr, 2 * nr, 0, 32, st));
+  STCHK(rocprim::exclusive_scan(nullptr, need, (const u32 *)nullptr, (u64 *)nullptr, (u64)0, 2 * nr + 1, rocprim::plus<u64>(), st));
+  if (need > tmp_bytes) tmp_bytes = need;
+  int rc;
+  if ((rc = ensure(ctx, &ctx->store.rx, cf_ws(nullptr, np, nr, msg_bytes, script_bytes, tmp_bytes).bytes)) != LAMD_OK) return rc;
+  const cf_ws w(ctx->store.rx.as<u8>(), np, nr, msg_bytes, script_bytes, tmp_bytes);
+  const bool timed = ctx->timing;
+  if (timed) STCHK(ctx->store.t_rx.create());
+  STCHK(hipMemcpyAsync(w.off2, rel.data(), 8 * (np + nr + 1), hipMemcpyHostToDevice, st));
+  if (np) {
+    STCHK(hipMemcpyAsync(w.pscid, pscid.data(), 8 * np, hipMemcpyHostToDevice, st));
+    STCHK(hipMemcpyAsync(w.pspk, pend_spk34, STORE_CA_SPK * np, hipMemcpyHostToDevice, st));
+    STCHK(hipMemsetAsync(w.first, 0xFF, 4 * np, st));
+  }
+  if (msg_bytes) STCHK(hipMemcpyAsync(w.msgs, pend_msgs + pend_off[0], msg_bytes, hipMemcpyHostToDevice, st));
+  if (script_bytes) STCHK(hipMemcpyAsync(w.scripts, r_scripts + r_script_off[0], script_bytes, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(w.r_scid, r_scid, 8 * nr, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(w.r_sat, r_sat, 8 * nr, hipMemcpyHostToDevice, st));
+  STCHK(hipMemcpyAsync(w.soff, srel.data(), 8 * (nr + 1), hipMemcpyHostToDevice, st));
+  STCHK(hipMemsetAsync(w.acnt, 0, 12 * (nr + 1), st));             // acnt, abytes, fcnt
+  STCHK(hipMemsetAsync(w.clr_key, 0xFF, 8 * nr, st));
+  STCHK(hipMemsetAsync(w.clr_head, 0, 4 * (2 * nr + 1), st));
+  STCHK(hipMemsetAsync(w.zero, 0, 4 * (np + nr), st));
+  STCHK(hipMemsetAsync(w.flags0, 0, np + nr, st));
+  const store_cf_view v{digest->scid, (u32)digest->count, digest->bare, (u32)digest->nbare, directory->img, directory->img_len, directory->rec_off,
+                        (u32)directory->n, directory->node_off, directory->node_nann, (u32)directory->nodes};
+  const store_cf_batch b{w.msgs, w.off2, w.pscid, w.pspk, (u32)np, w.r_scid, w.r_sat, w.scripts, w.soff, (u32)nr};
+  const dim3 grid(blocks_for(nr)), grid2(blocks_for(2 * nr)), block(256);
+  if (timed) STCHK(ctx->store.t_rx.record(0, st));
+  hipLaunchKernelGGL(k_ca_match, grid, block, 0, st, b, w.pend, w.first);
+  hipLaunchKernelGGL(k_ca_confirm, grid, block, 0, st, v, b, w.status, w.pend, (const u32 *)w.first, store_cf_marks{w.acnt, w.abytes, w.fcnt, w.clr_key});
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(1, st));
+  // node_announcements_not_dying(): the dying records of the accepted announcements' nodes, ascending, each once
+  STCHK(rocprim::radix_sort_keys(w.tmp, tmp_bytes, (const u32 *)w.clr_key, w.clr_sorted, 2 * nr, 0, 32, st));
+  hipLaunchKernelGGL(k_ca_clr_heads, grid2, block, 0, st, (u32)(2 * nr), (const u32 *)w.clr_sorted, w.clr_head);
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.clr_head, w.cpos, (u64)0, 2 * nr + 1, rocprim::plus<u64>(), st));
+  hipLaunchKernelGGL(k_ca_clr_write, grid2, block, 0, st, (u32)(2 * nr), (const u32 *)w.clr_sorted, (const u32 *)w.clr_head, (const u64 *)w.cpos, w.clr);
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.acnt, w.apos, (u64)0, nr + 1, rocprim::plus<u64>(), st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.abytes, w.abyte, (u64)0, nr + 1, rocprim::plus<u64>(), st));
+  STCHK(rocprim::exclusive_scan(w.tmp, tmp_bytes, (const u32 *)w.fcnt, w.fpos, (u64)0, nr + 1, rocprim::plus<u64>(), st));
+  hipLaunchKernelGGL(k_ca_plan, grid, block, 0, st, b, (const int8_t *)w.status, (const u32 *)w.pend, (const u64 *)w.apos, (const u64 *)w.abyte, (const u64 *)w.fpos,
+                     store_cf_plan_out{(u64)nr, (u64)nr, w.add_reply, w.add_off, w.fail_scid, w.rec_msg, w.rec_off, w.off2, w.msgs + msg_bytes, (u64)msg_bytes});
+  STCHK(hipGetLastError());
+  if (timed) STCHK(ctx->store.t_rx.record(2, st));
+  u64 totals[4] = {0, 0, 0, 0};
+  STCHK(hipMemcpyAsync(status, w.status, nr, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(pend, w.pend, 4 * nr, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[0], w.apos + nr, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[1], w.abyte + nr, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[2], w.fpos + nr, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipMemcpyAsync(&totals[3], w.cpos + 2 * nr, 8, hipMemcpyDeviceToHost, st));
+  STCHK(hipStreamSynchronize(st));   // the first wait: verdicts and sizes
+  if (timed) STCHK(ctx->store.t_rx.read(2, summary->stage_ms));
+  for (size_t r = 0; r < nr; r++) summary->by_status[status[r] < 0 || status[r] > 4 ? 1 : status[r]]++;
+  const u64 adds = totals[0], total = totals[1], fails = totals[2], clrs = totals[3];
+  summary->adds = adds;
+  summary->bytes = total;
+  summary->failures = fails;
+  summary->clears = clrs;
+  const bool want_out = out || d_out;
+  if (adds > add_cap) { ctx->err = "channel_announcement confirm: add_reply / add_off too small"; return LAMD_ERR_ARG; }
+  if (want_out && total > out_cap) { ctx->err = "channel_announcement confirm: output buffer too small"; return LAMD_ERR_ARG; }
+  if (fails > fail_cap) { ctx->err = "channel_announcement confirm: fail_scid too small"; return LAMD_ERR_ARG; }
+  if (clrs > clr_cap) { ctx->err = "channel_announcement confirm: clr_rec too small"; return LAMD_ERR_ARG; }
+  if (adds) {
+    STCHK(hipMemcpyAsync(add_reply, w.add_reply, 4 * adds, hipMemcpyDeviceToHost, st));
+    STCHK(hipMemcpyAsync(add_off, w.add_off, 8 * adds, hipMemcpyDeviceToHost, st));
+  }
+  if (fails) STCHK(hipMemcpyAsync(fail_scid, w.fail_scid, 8 * fails, hipMemcpyDeviceToHost, st));
+  if (clrs) STCHK(hipMemcpyAsync(clr_rec, w.clr, 4 * clrs, hipMemcpyDeviceToHost, st));
+  const bool encode = want_out && adds;
+  if (encode) {
+    if (!d_out && (rc = ensure(ctx, &ctx->store.rx_out, total + 16)) != LAMD_OK) return drain_fail(ctx, L, rc);
+    u8 *d_bytes = d_out ? (u8 *)d_out : ctx->store.rx_out.as<u8>();
+    const u64 words = (total + ((uintptr_t)d_bytes & 3) + 3) / 4;
+    const store_rx_batch eb{w.msgs, w.off2, (u32)(np + adds), nullptr, 0, nullptr, 0};   // the pending and the amount messages as the record encoder reads them
+    if (timed) STCHK(ctx->store.t_rx.record(5, st));
+    hipLaunchKernelGGL(k_rx_encode, dim3(blocks_for(2 * adds)), block, 0, st, (u32)(2 * adds), eb, (const u32 *)w.rec_msg, (const u8 *)w.flags0, (const u32 *)w.zero, w.hdr);
+    hipLaunchKernelGGL(k_rx_copy, dim3((unsigned)((words + 255) / 256)), block, 0, st, words,
+                       store_rx_out{w.rec_off, w.rec_msg, (u32)(2 * adds), w.hdr, w.msgs, w.off2}, d_bytes, total);
+    STCHK(hipGetLastError());
+    if (timed) STCHK(ctx->store.t_rx.record(6, st));
+    if (out) STCHK(hipMemcpyAsync(out, d_bytes, total, hipMemcpyDeviceToHost, st));
+  }
+  STCHK(hipStreamSynchronize(st));   // the second wait: the lists and the bytes
+  if (timed && encode) {
+    float ms = 0;
+    STCHK(hipEventElapsedTime(&ms, ctx->store.t_rx.ev[5], ctx->store.t_rx.ev[6]));
+    summary->stage_ms[2] = ms;
   }
   return LAMD_OK;
 }

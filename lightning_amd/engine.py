@@ -91,7 +91,8 @@ def gossip_store_frame(blob):
 
 def apply_update_plan(blob, rec_off, plan):
     """the plan of Engine.channel_update_receive applied to the image it was made for, in numpy: the DELETED bit of every del_rec set, the
-    headers of the set_rec announcements re-stamped (timestamp and crc), the added records appended behind the old end.
+    headers of the set_rec announcements re-stamped (timestamp and crc), the DYING bit of every clr_rec header cleared where the plan has that
+    key (Engine.channel_announcement_confirm's), the added records appended behind the old end.
     -> (image bytes, rec_off uint64 extended by the added records): audit it, or build digest, directory and stream index again"""
     img, n_bytes, _ = _store_blob(blob)
     if plan["records"] is None:
@@ -104,6 +105,8 @@ def apply_update_plan(blob, rec_off, plan):
         be = np.asarray(word, dtype=">u4").view(np.uint8).reshape(-1, 4)
         for x in range(4):
             out[at + k + x] = be[:, x]
+    if "clr_rec" in plan:
+        out[off[np.asarray(plan["clr_rec"], dtype=np.int64)].astype(np.int64)] &= 0xF7
     return out.tobytes(), np.concatenate([off, np.uint64(n_bytes) + np.asarray(plan["add_off"], dtype=np.uint64)])
 
 
@@ -914,6 +917,104 @@ class Engine:
         plan = dict(add_msg=add_msg[:s.adds], add_off=add_off[:s.adds], records=None if out is None else out[:s.bytes].tobytes(), del_rec=del_rec[:s.deletions],
                     set_rec=none, set_ts=none.copy(), set_crc=none.copy())
         res = (status[:n], flags[:n], node[:n], plan)
+        if return_summary:
+            res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
+
+    @staticmethod
+    def _msg_blob(msgs):
+        """a list of messages, or (blob uint8, off uint64 [n + 1]) -> (blob, off, n)"""
+        if isinstance(msgs, tuple):
+            blob, off = np.ascontiguousarray(msgs[0], dtype=np.uint8), np.ascontiguousarray(msgs[1], dtype=np.uint64)
+            n = off.size - 1
+            if n < 0 or (n and int(off[n]) > blob.size):
+                raise ValueError("the offsets do not fit the blob")
+            return blob, off, n
+        n = len(msgs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        return np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\x00", dtype=np.uint8), off, n
+
+    def channel_announcement_receive(self, digest, msgs, chain_hash, blockheight, held=(), failed=(), return_summary=False):
+        """lamd_channel_announcement_receive_batch: a drained queue of raw channel_announcement messages received against the digest of a store
+        image (built by this Engine): framing, the filters, ONE signature batch with four rows per message that passed them, the bitcoin keys alone
+        of the others, "already pending from this batch" in arrival order, the funding scripts.  msgs: a list of messages, or (blob uint8, off
+        uint64 [n + 1]).  blockheight 0: unknown.  held: the scids of the caller's pending and too-early maps, failed: of its txout failures.
+        -> (status int8 [msgs] (0 pending: ask lightningd, -1 malformed, 1 node ids not ordered, 2 foreign chain, 3 txout failed before, 4 known,
+        5 .. 8 the first bad signature, 9 bad gossip order, 10 already pending from this batch, 11 early), scid uint64 [msgs] (0: malformed),
+        spk uint8 [msgs, 34] (the expected scriptpubkey for the statuses 0 and 11, zeros otherwise), asks = dict(msg uint32 [asks], scid uint64
+        [asks]): the get_txout requests in arrival order)"""
+        chain = np.frombuffer(bytes(chain_hash), dtype=np.uint8)
+        if chain.size != 32:
+            raise ValueError("the chain_hash has 32 bytes")
+        blob, off, n = self._msg_blob(msgs)
+        hs = np.array(sorted(set(int(s) for s in held)) + [0], dtype=np.uint64)
+        fs = np.array(sorted(set(int(s) for s in failed)) + [0], dtype=np.uint64)
+        cap = max(1, n)
+        status, scid, spk = np.zeros(cap, dtype=np.int8), np.zeros(cap, dtype=np.uint64), np.zeros((cap, 34), dtype=np.uint8)
+        ask_msg, ask_scid = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint64)
+        s = _ffi.LamdAnnounceReceiveSummary()
+        self._chk(self._lib.lamd_channel_announcement_receive_batch(
+            self._ctx, digest._h, chain.ctypes.data, int(blockheight), n, blob.ctypes.data, off.ctypes.data, hs.size - 1, hs.ctypes.data, fs.size - 1,
+            fs.ctypes.data, status.ctypes.data, scid.ctypes.data, spk.ctypes.data, cap, ask_msg.ctypes.data, ask_scid.ctypes.data, ctypes.byref(s)))
+        res = (status[:n], scid[:n], spk[:n], dict(msg=ask_msg[:s.asks], scid=ask_scid[:s.asks]))
+        if return_summary:
+            res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
+        return res
+
+    def channel_announcement_confirm(self, digest, directory, pending_msgs, pending_spk, replies, d_out=None, host_out=True, return_summary=False):
+        """lamd_channel_announcement_confirm_batch: lightningd's txout replies against the caller's pending announcements and the digest and
+        directory of the image as it is now.  pending_msgs: the raw announcements STRICTLY ASCENDING by scid (a list, or (blob, off)); pending_spk:
+        their scripts from channel_announcement_receive, uint8 [pending, 34]; replies: a list of (scid, sat, script bytes) in arrival order, or the four
+        arrays GossipIngest.txout_reply_batch takes (scid, sat, scripts, script_off).
+        -> (status int8 [replies] (0 accepted, 1 nothing pending, 2 no unspent output, 3 another script, 4 redundant), pend uint32 [replies] (the
+        pending message consumed, 0xFFFFFFFF: none), fail_scid uint64 (the statuses 2 and 3: the caller's new txout failures), plan): plan =
+        dict(add_reply uint32 [adds], add_off uint64 [2 adds] (the offset of EVERY record: the announcement and the channel_amount of each accepted
+        reply), records bytes or None (without host_out), clr_rec uint32 ascending (node_announcement headers whose DYING bit is cleared),
+        del_rec / set_rec / set_ts / set_crc: empty) -- apply_update_plan() applies it to the image"""
+        blob, off, np_ = self._msg_blob(pending_msgs)
+        pspk = np.ascontiguousarray(pending_spk, dtype=np.uint8).reshape(-1)
+        if pspk.size != 34 * np_:
+            raise ValueError("one 34-byte script per pending announcement")
+        pspk = np.concatenate([pspk, np.zeros(1, dtype=np.uint8)])
+        if isinstance(replies, tuple):                    # (scid uint64 [nr], sat uint64 [nr], scripts uint8, script_off uint64 [nr + 1]): as txout_reply_batch takes them
+            r_scid, r_sat = (np.concatenate([np.asarray(a, dtype=np.uint64), np.zeros(1, dtype=np.uint64)]) for a in replies[:2])
+            scripts, soff = np.ascontiguousarray(replies[2], dtype=np.uint8), np.ascontiguousarray(replies[3], dtype=np.uint64)
+            nr = soff.size - 1
+            if nr < 0 or r_scid.size != nr + 1 or r_sat.size != nr + 1 or (nr and int(soff[nr]) > scripts.size):
+                raise ValueError("the replies' arrays do not fit each other")
+            scripts = np.concatenate([scripts, np.zeros(1, dtype=np.uint8)])
+        else:
+            nr = len(replies)
+            r_scid = np.array([int(r[0]) for r in replies] + [0], dtype=np.uint64)
+            r_sat = np.array([int(r[1]) for r in replies] + [0], dtype=np.uint64)
+            soff = np.zeros(nr + 1, dtype=np.uint64)
+            soff[1:] = np.cumsum([len(r[2]) for r in replies], dtype=np.uint64)
+            scripts = np.frombuffer(b"".join(bytes(r[2]) for r in replies) + b"\x00", dtype=np.uint8)
+        # a pending message is appended once at most: its bytes, two headers and the amount (d_out must hold this much)
+        cap, nbytes = max(1, nr), max(1, int(off[np_] - off[0]) + 34 * min(nr, np_))
+        status, pend = np.zeros(cap, dtype=np.int8), np.zeros(cap, dtype=np.uint32)
+        add_reply, add_off, fail_scid, clr_rec = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64), np.zeros(2 * cap, dtype=np.uint32)
+        out = np.zeros(nbytes, dtype=np.uint8) if host_out else None
+        d_ptr = None
+        if d_out is not None:
+            if d_out.numel() < nbytes:
+                raise ValueError("d_out must hold the pending messages and 34 bytes per reply")
+            self._after_torch()
+            d_ptr = d_out.data_ptr()
+        s = _ffi.LamdAnnounceConfirmSummary()
+        self._chk(self._lib.lamd_channel_announcement_confirm_batch(
+            self._ctx, digest._h, directory._h, np_, blob.ctypes.data, off.ctypes.data, pspk.ctypes.data, nr, r_scid.ctypes.data, r_sat.ctypes.data,
+            scripts.ctypes.data, soff.ctypes.data, status.ctypes.data, pend.ctypes.data, cap, add_reply.ctypes.data, add_off.ctypes.data,
+            None if out is None else out.ctypes.data, d_ptr, nbytes, cap, fail_scid.ctypes.data, 2 * cap, clr_rec.ctypes.data, ctypes.byref(s)))
+        none = np.zeros(0, dtype=np.uint32)
+        first = add_off[:s.adds]
+        took = pend[add_reply[:s.adds]].astype(np.int64)
+        lens = (off[took + 1] - off[took]).astype(np.uint64)
+        both = np.stack([first, first + np.uint64(12) + lens], axis=1).reshape(-1) if s.adds else np.zeros(0, dtype=np.uint64)
+        plan = dict(add_reply=add_reply[:s.adds], add_off=both, records=None if out is None else out[:s.bytes].tobytes(), clr_rec=clr_rec[:s.clears],
+                    del_rec=none, set_rec=none.copy(), set_ts=none.copy(), set_crc=none.copy())
+        res = (status[:nr], pend[:nr], fail_scid[:s.failures], plan)
         if return_summary:
             res += ({k: (list(getattr(s, k)) if k in ("stage_ms", "by_status") else int(getattr(s, k))) for k, _ in s._fields_},)
         return res
